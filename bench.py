@@ -5,6 +5,17 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1 it i
 `python -m torch.distributed.run --nproc-per-node N ...` (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from env).
 Rank 0 prints ONE JSON line.
 
+A plain run does what the headline figure needs and nothing else: set-up, the settle steps, W warm-ups, exactly K timed steps, the outputs of
+the last timed step if `--dump-outputs DIR` asks for them, the JSON line (metric / value / unit / higher_is_better / dtype / ms_per_step, the
+workload's config, reset rate and mean reward of the timed steps).  Everything else described below -- the repeated regions, `pooled`, the
+HIP-event kernel time and `roofline`, the side legs `extra` / `extra2` / `extra3` / `shard_legs`, `box`, `cpu_baseline` -- is measured with
+`--full` only (the `--no-*` switches then drop parts of it).
+
+  --dump-outputs DIR = what the caller of the K-th timed `env.step()` received, as DIR/<name>.npy in float32: `obs` (and `states` where the task
+              has them), `rew`, `reset`, `time_outs`.  The env and the action generator are seeded and the number of untimed steps is fixed, so the
+              same arguments give the same inputs in every run: two builds can be compared output for output.  More than 64 MB in all
+              (only with a --num-envs far above the BASELINE sizes) is cut down to a fixed, seeded sample of env rows (`rows.npy` holds them).
+
   step      = one `env.step(actions)` through the public Python API (isaacgymenvs_amd.make -> VecTask.step), i.e.
               one launch group (sub-step kernels + post kernel, no host sync) advancing every env by one control
               step (reference vec_task.py:360-408).
@@ -30,11 +41,12 @@ Rank 0 prints ONE JSON line.
               driver run does not quote them on the first steps of the first episode.
   --scaling strong : BASELINE's "per-GPU shard = N/G" reading -- Ant 4096 / N and Humanoid 8192 / N envs per GPU ("scaling": "strong");
               the default is weak scaling (4096 / 8192 per GPU).
-  settle    = untimed steps run before the W warm-ups of the headline leg: at least 100 - W ("warm-up 100 steps") and at least 0.5 s
-              of back-to-back stepping: the first step resets every env (reset_buf starts at 1, vec_task.py:316) and a fresh episode has no
+  settle    = untimed steps run before the W warm-ups of the headline leg: SETTLE_STEPS of them, a fixed count (the inputs of the timed steps must
+              not depend on the host's speed) that covers SURVEY 8d's "warm-up 100 steps" and is about 0.5 s of back-to-back stepping at the
+              headline size: the first step resets every env (reset_buf starts at 1, vec_task.py:316) and a fresh episode has no
               falls / resets yet, i.e. less work than the steady state; and a leg starts on a GPU that idled through the host-side set-up.
   value / ms_per_step = the contract's literal region: W warm-ups, then exactly K steps between two barrier + synchronize pairs.
-  timed_regions / regions_ms_per_step / median_region = with K < 500 the same K-step region is timed again until ~1000 steps are in (diagnostic:
+  timed_regions / regions_ms_per_step / median_region = (--full) with K < 500 the same K-step region is timed again until ~1000 steps are in (diagnostic:
               how noisy a 1 ms region is); the first list entry is the region `value` is computed from.
   legs carry `consistent` = the HIP-event time of a step's launch group fits inside the wall-clock step (kernel_ms * 0.9 <= pooled ms).
 """
@@ -53,7 +65,11 @@ if ROOT not in sys.path:
 # API-visible state read once + written once per env-step
 ALGO_BYTES = {"Cartpole": 89, "Ant": 673, "Humanoid": 1161, "AnymalTerrain": 2240, "ShadowHand": 3600}
 DEFAULT_ENVS = {"Cartpole": 64, "Ant": 4096, "Humanoid": 8192, "AnymalTerrain": 4096, "ShadowHand": 16384}
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E ~8 TB/s
+HBM_PEAK_GBS = 8000.0  # HBM3E ~8 TB/s
+# untimed steps before the warm-ups of the headline leg (docstring, `settle`): about 0.5 s of Ant@4096 stepping.  A count, not a duration: with
+# a duration the timed steps would start from a state that depends on how fast the host enqueues, and --dump-outputs could not be compared.
+SETTLE_STEPS = 11000
+DUMP_MAX_BYTES = 64 << 20
 # chip-wide VALU issue peak in wave-instructions (/opt/skills/guides/MI355X_MICROARCH.md, "Wave scheduling" + the cycle-constants table): 256 CUs x
 # 4 SIMD-32 units, a wave64 VALU instruction issues over 2 cycles (32 lanes per cycle) at 2.4 GHz -> 1228.8 G wave-instructions/s; x 64 lanes x 2
 # FLOP (fma) = the 157.3 TFLOP/s fp32 vector spec.  ONE wave on a SIMD issues at most every ~4 cycles (in-order, dependent-issue latency), so
@@ -108,9 +124,27 @@ def leg_consistent(res):
     return res["kernel_ms_avg"] * 0.9 <= res["ms_per_step"]
 
 
-def measure(task, num_envs, steps, warmup, device, rank, world, seed=42, pool=8, settle=0, settle_s=0.0):
-    """Times `steps` control steps twice: with the reference's protocol (actions drawn by torch.rand right before every step,
-    README.md:48-51 -- this is the reported value) and with a small pool of pre-generated action batches (engine only)."""
+def dump_outputs(out, path, seed=42):
+    """--dump-outputs: the tuple one `env.step()` returned, as float32 .npy files (a seeded sample of env rows above DUMP_MAX_BYTES in all)."""
+    import numpy as np
+    obs, rew, reset, extras = out
+    arrays = {k: obs[k] for k in ("obs", "states") if k in obs}
+    arrays.update(rew=rew, reset=reset, time_outs=extras["time_outs"])
+    arrays = {k: v.detach().to("cpu").numpy().astype(np.float32) for k, v in arrays.items()}
+    total, n = sum(a.nbytes for a in arrays.values()), len(arrays["rew"])
+    if total > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=max(1, n * DUMP_MAX_BYTES // total), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def measure(task, num_envs, steps, warmup, device, rank, world, seed=42, pool=8, settle=0, full=True, dump=None):
+    """Times `steps` control steps with the reference's protocol (actions drawn by torch.rand right before every step, README.md:48-51 -- this
+    is the reported value); with `full`, again with a small pool of pre-generated action batches (engine only), in repeated regions and
+    launch group by launch group.  `dump`: a directory for the outputs of the last timed step (rank 0)."""
     import torch
     import torch.distributed as dist
     import isaacgymenvs_amd
@@ -131,44 +165,36 @@ def measure(task, num_envs, steps, warmup, device, rank, world, seed=42, pool=8,
             dist.barrier()
         torch.cuda.synchronize()
 
+    last = [None]       # what the last step of the last timed() call returned (the engine's own buffers: the next step overwrites them)
+
     def timed(fresh, steps=steps):
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        out = None
         t0 = time.perf_counter()
         ev0.record()
         for i in range(steps):
             a = 2.0 * torch.rand((num_envs, na), device=device, generator=g) - 1.0 if fresh else acts[i % pool]
-            env.step(a)
+            out = env.step(a)
             if reducer:
                 reducer.step()
         ev1.record()
         sync()
         wall = time.perf_counter() - t0
         gpu_ms = ev0.elapsed_time(ev1)
+        last[0] = out
         if use_dist:
             t = torch.tensor([wall], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             wall = float(t.item())
         return wall, gpu_ms
 
-    # settle: untimed steps BEFORE the contract's W warm-ups -- at least `settle` of them and at least `settle_s` seconds of back-to-back stepping, so
-    # that the timed region starts on a device at its steady clocks (a leg starts after ~100 ms of host-side set-up with the GPU idle) and on
-    # episodes at their steady-state reset rate.  Every rank runs the same count (rank 0's) so the reducer's collectives stay matched.
-    t_settle, settled = time.perf_counter(), 0
-    while True:
-        more = settled < settle or time.perf_counter() - t_settle < settle_s
-        if use_dist:
-            flag = torch.tensor([1 if more else 0], device=device)
-            dist.broadcast(flag, 0)
-            more = bool(flag.item())
-        if not more:
-            break
-        for _ in range(50 if settled >= settle else max(settle - settled, 1)):
-            env.step(2.0 * torch.rand((num_envs, na), device=device, generator=g) - 1.0)
-            if reducer:
-                reducer.step()
-            settled += 1
-        torch.cuda.synchronize()
-    settle = settled
+    # settle: `settle` untimed steps BEFORE the contract's W warm-ups, so that the timed region starts on a device at its steady clocks (a leg
+    # starts after ~100 ms of host-side set-up with the GPU idle) and on episodes at their steady-state reset rate
+    for _ in range(settle):
+        env.step(2.0 * torch.rand((num_envs, na), device=device, generator=g) - 1.0)
+        if reducer:
+            reducer.step()
+    torch.cuda.synchronize()
     # the W warm-ups go through the SAME code path as the timed steps (the loop, the events, the closing barrier + synchronize of timed()):
     # what a first pass through that path costs once -- event pools, lazily initialised timing state, the first all-reduce of the wall time --
     # is warm-up cost, not part of the K timed steps (round 5: the first 20-step region read 0.052 ms per step, every later one 0.045-0.047)
@@ -181,37 +207,13 @@ def measure(task, num_envs, steps, warmup, device, rank, world, seed=42, pool=8,
     torch.cuda.synchronize()
     wall, gpu_ms = timed(True)
     stats = (env.engine.tensors["episode_stats"] - stats0).cpu().tolist()
-    # `value` / `ms_per_step` are THIS region: W warm-ups, then exactly K steps between two barrier + synchronize pairs (the driver's contract,
-    # read literally).  A short region (the driver's --steps 20 is 1 ms of GPU time) is noisy, so the same K-step region is timed again until
-    # about 1000 steps are in; every region's time is kept in `regions_ms_per_step` and their median in `median_region` -- a diagnostic beside
-    # the value, not the value.
-    regions = [(wall, gpu_ms)]
-    for _ in range(min(24, max(0, -(-1000 // max(steps, 1)) - 1)) if steps < 500 else 0):
-        regions.append(timed(True))
-    regions_ms = [1e3 * w / steps for w, _ in regions]
-    med_wall = sorted(w for w, _ in regions)[len(regions) // 2]
-    wall_pool, _ = timed(False)
-    # per-launch duration of the fused step (sub-step kernels + post kernel): HIP events on the launch stream around each launch group
-    kn = 200
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(kn)]
-    torch.cuda.synchronize()
-    for i, (a, b) in enumerate(pairs):
-        a.record()
-        env.engine.step(acts[i % pool])
-        b.record()
-    torch.cuda.synchronize()
-    durs = sorted(a.elapsed_time(b) for a, b in pairs)
-    kern_ms = sum(durs) / len(durs)
+    if dump and rank == 0:
+        dump_outputs(last[0], dump, seed)
     res = {
-        "task": task, "num_envs_per_gpu": num_envs, "wall_s": wall, "ms_per_step": 1e3 * wall / steps,
-        "gpu_ms_per_step": gpu_ms / steps, "kernel_ms_avg": kern_ms, "kernel_ms_median": durs[len(durs) // 2],
+        "task": task, "num_envs_per_gpu": num_envs, "wall_s": wall, "ms_per_step": 1e3 * wall / steps, "gpu_ms_per_step": gpu_ms / steps,
         "env_steps_per_s": world * num_envs * steps / wall,
-        "pooled": {"ms_per_step": 1e3 * wall_pool / steps, "env_steps_per_s": world * num_envs * steps / wall_pool,
-                   "note": f"same loop with a pool of {pool} pre-generated action batches instead of torch.rand per step"},
         "reset_rate": stats[2] / max(stats[4], 1.0), "mean_reward": stats[3] / max(stats[4], 1.0),
         "multi_wave": int(env.engine.get_option("multi_wave")), "steps": steps, "warmup": warmup, "settle": settle,
-        "timed_regions": len(regions), "regions_ms_per_step": [round(x, 5) for x in regions_ms],
-        "median_region": {"ms_per_step": 1e3 * med_wall / steps, "env_steps_per_s": world * num_envs * steps / med_wall},
     }
     try:
         res["fused_sub"] = int(env.engine.get_option("fused_sub"))     # all sub-steps of a control step in one launch (Ant, AnymalTerrain)
@@ -221,9 +223,35 @@ def measure(task, num_envs, steps, warmup, device, rank, world, seed=42, pool=8,
         res["fused_post"] = int(env.engine.get_option("fused_post"))   # Ant: post_physics_step inside that launch too, spread over the four role waves
     except RuntimeError:
         res["fused_post"] = 0
-    res["consistent"] = bool(leg_consistent(res))
     if task == "Humanoid":
         res["self_collision"] = int(env.engine.get_option("self_collision"))
+    if full:
+        # `value` / `ms_per_step` are the region above: W warm-ups, then exactly K steps between two barrier + synchronize pairs (the driver's
+        # contract, read literally).  A short region (the driver's --steps 20 is 1 ms of GPU time) is noisy, so the same K-step region is timed
+        # again until about 1000 steps are in; every region's time is kept in `regions_ms_per_step` and their median in `median_region` -- a
+        # diagnostic beside the value, not the value.
+        regions = [(wall, gpu_ms)]
+        for _ in range(min(24, max(0, -(-1000 // max(steps, 1)) - 1)) if steps < 500 else 0):
+            regions.append(timed(True))
+        med_wall = sorted(w for w, _ in regions)[len(regions) // 2]
+        wall_pool, _ = timed(False)
+        # per-launch duration of the fused step (sub-step kernels + post kernel): HIP events on the launch stream around each launch group
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(200)]
+        torch.cuda.synchronize()
+        for i, (a, b) in enumerate(pairs):
+            a.record()
+            env.engine.step(acts[i % pool])
+            b.record()
+        torch.cuda.synchronize()
+        durs = sorted(a.elapsed_time(b) for a, b in pairs)
+        res.update({
+            "kernel_ms_avg": sum(durs) / len(durs), "kernel_ms_median": durs[len(durs) // 2],
+            "pooled": {"ms_per_step": 1e3 * wall_pool / steps, "env_steps_per_s": world * num_envs * steps / wall_pool,
+                       "note": f"same loop with a pool of {pool} pre-generated action batches instead of torch.rand per step"},
+            "timed_regions": len(regions), "regions_ms_per_step": [round(1e3 * w / steps, 5) for w, _ in regions],
+            "median_region": {"ms_per_step": 1e3 * med_wall / steps, "env_steps_per_s": world * num_envs * steps / med_wall},
+        })
+        res["consistent"] = bool(leg_consistent(res))
     if reducer:
         res["job_stats"] = reducer.result()
     del env
@@ -446,9 +474,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--task", default="Ant", choices=list(DEFAULT_ENVS))
     ap.add_argument("--num-envs", type=int, default=0, help="envs per GPU (default: the BASELINE config of the task)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the Humanoid@8192 side measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shard-legs", action="store_true", help="skip the 1/8-shard legs (AnymalTerrain@512, ShadowHand@2048); the profiling recipe "
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure as well: repeated regions, pooled actions, kernel "
+                    "time and roofline, the side legs (other tasks and shard sizes), the box probe, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline leg returned (obs, rew, reset, ...) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side legs (Humanoid@8192, AnymalTerrain, ShadowHand)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-shard-legs", action="store_true", help="with --full: skip the 1/8-shard legs (AnymalTerrain@512, ShadowHand@2048); the profiling recipe "
                     "sets it so that a kernel's counters are not averaged over two launch sizes")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: the BASELINE env count PER GPU (default); strong: the BASELINE env count split over the GPUs (N/G per GPU)")
@@ -456,7 +488,7 @@ def main():
     ap.add_argument("--pool", type=int, default=8,
                     help="number of pre-generated U(-1,1) action batches cycled through.  The reference protocol draws the actions with "
                          "torch.rand right before every step (README.md:48-51), i.e. they are cache-hot when step() reads them; a small "
-                         "pool reproduces that without timing torch.rand (a pool of 64 distinct batches made every read a cold miss, +5 %)")
+                         "pool reproduces that without timing torch.rand (a pool of 64 distinct batches made every read a cold miss, +5 %%)")
     args = ap.parse_args()
 
     # stdout carries ONE line, the JSON record of rank 0: whatever the legs print on the way (the reference's "Forcing CPU Pipeline" notice of the
@@ -494,12 +526,12 @@ def main():
             side["Humanoid"] = max(DEFAULT_ENVS["Humanoid"] // world, 64)
     # side legs: long enough to be steady-state numbers whatever K / W the driver passes for the headline
     sk, sw = max(args.steps // 4, 200), max(args.warmup // 4, 50)
-    if not args.no_extra and args.task == "Ant":
+    if args.full and not args.no_extra and args.task == "Ant":
         extra = measure("Humanoid", side["Humanoid"], sk, sw, device, rank, world)
         extra2 = measure("AnymalTerrain", side["AnymalTerrain"], sk, sw, device, rank, world)
         extra3 = measure("ShadowHand", side["ShadowHand"], sk, sw, device, rank, world)
     shard_legs = None
-    if world == 1 and not args.no_extra and not args.no_shard_legs and args.task == "Ant":
+    if args.full and world == 1 and not args.no_extra and not args.no_shard_legs and args.task == "Ant":
         # BASELINE configs 4 / 5 are quoted "sharded across 8 GPUs": what ONE GPU then runs is 4096 / 8 and 16384 / 8 envs.  Their step times at
         # N = 1 put the strong-scaling expectation on record: these sizes sit on the launch-latency floor (a step of 512 AnymalTerrain envs costs
         # about what 4096 cost), so 8 GPUs x 1/8 of the envs deliver roughly what one GPU delivers -- per-GPU efficiency ~ 1/8 by construction.
@@ -515,12 +547,12 @@ def main():
                 "expected_8gpu_strong_scaling_efficiency": (8 * r["env_steps_per_s"] / ref["env_steps_per_s"]) / 8.0,
                 "note": f"1/8 shard of BASELINE's {t}@{full} on ONE GPU; 8 such shards = the strong-scaling job. "
                         "expected efficiency = (8 x this rate / the full-size single-GPU rate) / 8: latency-floor-bound, see DESIGN.md 6"}
-    # The headline configuration is measured last (W untimed warm-ups + exactly K timed steps, after `settle` more untimed steps that
+    # The headline configuration is measured last (W untimed warm-ups + exactly K timed steps, after SETTLE_STEPS more untimed steps that
     # bring the episodes to their steady-state reset rate): with the driver's short runs (K = 20, W = 5, i.e. 1.5 ms of GPU work) it
     # would otherwise be timed on a device that is still ramping its clocks up from idle, on envs that were all reset one step ago.
-    settle = max(100 - args.warmup, 0)
-    main_res = measure(args.task, n_env, args.steps, args.warmup, device, rank, world, pool=args.pool, settle=settle, settle_s=0.5)
-    settle = main_res["settle"]
+    settle = SETTLE_STEPS
+    main_res = measure(args.task, n_env, args.steps, args.warmup, device, rank, world, pool=args.pool, settle=settle, full=args.full,
+                       dump=args.dump_outputs)
     import torch.distributed as dist
     if rank != 0:
         if dist.is_initialized():
@@ -534,16 +566,15 @@ def main():
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"{args.task} num_envs={n_env} per GPU ({world * n_env} total), VecTask.step() via Python API, "
                                f"actions = 2*torch.rand-1 drawn before every step (README.md:48-51), seed 42+rank; {settle} untimed settle steps "
-                               f"(>= 0.5 s of back-to-back stepping) precede the {args.warmup} warm-ups",
+                               f"(about 0.5 s of back-to-back stepping at the BASELINE size) precede the {args.warmup} warm-ups",
                    "task": args.task, "num_envs_per_gpu": n_env, "parallelism": f"env-shard x{world}",
                    "multi_wave": main_res["multi_wave"], "fused_sub": main_res["fused_sub"], "fused_post": main_res.get("fused_post", 0)},
-        "settle": settle, "consistent": main_res["consistent"],
-        "timed_regions": main_res["timed_regions"], "regions_ms_per_step": main_res["regions_ms_per_step"],
-        "median_region": main_res["median_region"],
-        "gpu_ms_per_step": main_res["gpu_ms_per_step"], "reset_rate": main_res["reset_rate"],
-        "mean_reward": main_res["mean_reward"], "pooled": main_res["pooled"],
-        "roofline": roofline(args.task, n_env, main_res["kernel_ms_avg"], main_res["multi_wave"]),
+        "settle": settle, "gpu_ms_per_step": main_res["gpu_ms_per_step"], "reset_rate": main_res["reset_rate"],
+        "mean_reward": main_res["mean_reward"],
     }
+    if args.full:
+        out.update({k: main_res[k] for k in ("consistent", "timed_regions", "regions_ms_per_step", "median_region", "pooled")})
+        out["roofline"] = roofline(args.task, n_env, main_res["kernel_ms_avg"], main_res["multi_wave"])
     if dist.is_initialized():
         # what the collective layer actually spans (the driver's N>1 launches): torch.distributed world size, backend ("nccl" IS RCCL on ROCm)
         out["dist_world_size"] = dist.get_world_size()
@@ -577,8 +608,9 @@ def main():
                          "roofline": roofline("ShadowHand", side["ShadowHand"], extra3["kernel_ms_avg"], extra3["multi_wave"])}
         if "job_stats" in extra3:
             out["extra3"]["job_stats"] = extra3["job_stats"]
-    out["box"] = box_probe(device)
-    if world == 1 and not args.no_cpu_baseline and args.task in ("Ant", "Humanoid"):
+    if args.full:
+        out["box"] = box_probe(device)
+    if args.full and world == 1 and not args.no_cpu_baseline and args.task in ("Ant", "Humanoid"):
         # `value` = the like-for-like figure: the engine's own CPU backend through make(..., "cpu", "cpu") at the reference's `num_threads: 4`
         # (cfg/config.yaml:30).  The oracle port's thread sweep and the reference's own jitted functions are nested beside it.
         port = cpu_baseline(args.task, n_env, budget_s=args.cpu_budget)

@@ -69,8 +69,8 @@ def test_init_state_writes_everything_the_step_reads(task, monkeypatch):
 def test_bench_line_is_the_last_stdout_line_when_a_process_group_is_up():
     """`bench.py --gpus N` under torchrun prints ONE JSON line on rank 0 (the driver parses it).  RCCL prints a version banner to the C-level
     stdout when its first communicator comes up; through a pipe that banner used to land AFTER the JSON line.  Exercised here with a one-rank
-    process group over RCCL (MI_FORCE_DIST=1: the same code path as N > 1 -- barriers, MAX all-reduce of the region time, the settle loop's
-    broadcast, the statistics reducers)."""
+    process group over RCCL (MI_FORCE_DIST=1: the same code path as N > 1 -- barriers, MAX all-reduce of the region time, the
+    statistics reducers)."""
     import json
     import subprocess
     import sys

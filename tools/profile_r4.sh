@@ -3,11 +3,12 @@
 # counters -- never combined with tracing), and the same two byte counters on the known-byte-count calibration kernels.
 # Usage: tools/profile_r3.sh <tag>   ->  gpurun_out/prof_<tag>/ ; then tools/summarize_profile.py <tag> here.
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-r4}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $GRAFT_REPO_ROOT/bench.py --steps 400 --warmup 40 --no-cpu-baseline"
+BENCH="python $ROOT/bench.py --full --steps 400 --warmup 40 --no-cpu-baseline"
 CAL=$GRAFT_REPO_ROOT/tools/calib/calib_fetch
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o $TAG -- $BENCH > $OUT/trace.log 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o $TAG -- $BENCH > $OUT/pmc_fetch.log 2>&1

@@ -121,17 +121,31 @@ typedef struct {
 /* The SCENE beside a fixed-base articulated actor: what the other actors of the reference's table-top envs become (franka_cube_stack.py:204-233,
  * 323-339: gym.create_box assets -- the table and its stand with fix_base_link, two free cubes -- created in every env beside the arm).  Free boxes
  * are rigid bodies of the same sub-step (contacts with the actor's collision spheres, the static boxes, the ground plane and each other are rows of
- * the one Gauss-Seidel solve, csrc/core/scene_engine.hpp); their root states live in tensor "scene_state" [N, MI_SCENE_MAX_FREE, 13]. */
+ * the one Gauss-Seidel solve, csrc/core/scene_engine.hpp); their root states live in tensor "scene_state" [N, MI_SCENE_MAX_FREE, 13].
+ * A free body has a SHAPE (free_shape): box, sphere or capsule (gym.create_box / create_sphere / create_capsule); static bodies are boxes.  A round
+ * body is a core segment plus a radius (a sphere's segment is a point).  Contact sets, every contact 3 rows (normal + friction disc):
+ *   box   vs ground plane / static box / free box: corners in boxes (both directions), edge x edge, outline crossings of a face contact
+ *   round vs ground plane: one contact per core end point (sphere 1, capsule 2)
+ *   round vs static box / free box: sphere-box at each core end point (exact for a sphere); a capsule also at the interior point of its segment
+ *         nearest to the box (a capsule across a knife edge) -- capsule vs box is an approximation by those three points
+ *   round vs round: closest points of the two core segments, one contact; two at the ends of the overlap of parallel capsules
+ *   actor collision sphere vs free body: sphere-box, or the closest point of a round body's core segment
+ * The capsule's axis is the body's local x (what gym.create_capsule(radius, length) is taken to make; like all physics here this convention is
+ * unpinned against the closed simulator). */
 #define MI_SCENE_MAX_FREE 4
 #define MI_SCENE_MAX_STATIC 4
+#define MI_SHAPE_BOX 0
+#define MI_SHAPE_SPHERE 1
+#define MI_SHAPE_CAPSULE 2
 #define MI_SCENE_WARM_SLOTS 48 /* entries per env of tensor "scene_warm": one per contact slot of the scene solve (24 actor + 24 box contacts) */
 typedef struct {
     int32_t n_free, n_static;              /* 0, 0: no scene -- the actor alone on the ground plane (its spheres against the plane) */
     int32_t arm_gravity;                   /* 0: asset option disable_gravity on the articulated actor (franka_cube_stack.py:199); the boxes feel the sim's */
-    int32_t pad;
-    float free_half[MI_SCENE_MAX_FREE][3]; /* half sizes */
+    int32_t free_shape;                    /* 4 bits per free body i, (free_shape >> 4 * i) & 15: 0 box, 1 sphere, 2 capsule (MI_SHAPE_*); 0: all boxes.
+                                            * Another code is refused by mi_engine_create (mi_last_error) */
+    float free_half[MI_SCENE_MAX_FREE][3]; /* box: half sizes; sphere: {r, r, r}; capsule: {half length of the cylinder part, r, r}, axis along local x */
     float free_mass[MI_SCENE_MAX_FREE];
-    float free_inertia[MI_SCENE_MAX_FREE][3];  /* principal inertias along the box axes */
+    float free_inertia[MI_SCENE_MAX_FREE][3];  /* principal inertias along the body axes */
     float free_mu[MI_SCENE_MAX_FREE];      /* shape friction (combined with the other side's by averaging) */
     float free_init[MI_SCENE_MAX_FREE][7]; /* start pose (create_actor): position, quaternion xyzw */
     float static_pos[MI_SCENE_MAX_STATIC][3], static_quat[MI_SCENE_MAX_STATIC][4], static_half[MI_SCENE_MAX_STATIC][3], static_mu[MI_SCENE_MAX_STATIC];
@@ -142,7 +156,7 @@ typedef struct {
     float kp[MI_MAX_DOF], kd[MI_MAX_DOF];  /* per-dof position-drive gains; kp = kd = 0: no drive on that dof */
     float max_angular_velocity;            /* asset option: clamp of the base's angular speed (rad/s); <= 0: none */
     float init_root[13];                   /* actor start pose (create_actor) + zero velocities */
-    MiScene scene;                         /* free / static boxes beside the actor; fixed-base actors only */
+    MiScene scene;                         /* free bodies / static boxes beside the actor; fixed-base actors only */
     float drive_vmax[MI_MAX_DOF];          /* the asset's joint velocity limits (URDF <limit velocity=>); <= 0: none.  Scenes only: the solved joint velocities
                                             * are clamped to them (the simulator's maxJointVelocity), and a position drive's error is clamped to vmax * kd / kp,
                                             * the error at which its spring and damper balance at that speed (franka_panda_gripper.urdf:247 fingers: 0.2 m/s) */

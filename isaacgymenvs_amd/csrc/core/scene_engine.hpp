@@ -1,4 +1,5 @@
-// scene_engine.hpp -- physics sub-step of a fixed-base articulated actor in a SCENE: free rigid boxes and static boxes beside it.
+// scene_engine.hpp -- physics sub-step of a fixed-base articulated actor in a SCENE: free rigid bodies (boxes, spheres, capsules) and static boxes
+// beside it.
 //
 // Replaces gym.simulate() for the reference's table-top manipulation tasks, whose envs hold more than one actor: reference
 // isaacgymenvs/tasks/franka_cube_stack.py:204-233,323-339 (the Franka arm, a table and its stand -- static boxes, gym.create_box with
@@ -17,6 +18,20 @@
 //     and corner-face configurations (a cube on a table, a cube stacked on a cube, a cube pushed against a cube, a plate on a smaller stand) --
 //     plus the edge-edge contact of crossed edges and the outline crossings of a face contact (crossed planks, a plank on a knife edge).  A stated approximation like every contact model here: physics parity against PhysX is
 //     unpinned.
+//   * free bodies have a SHAPE (SceneParams::free_shape, 4 bits per body: 0 box, 1 sphere, 2 capsule along the body's local x).  A ROUND body is a
+//     core segment plus a radius (a sphere's segment is a point); its contacts live in the box-contact slots, side A = the round body:
+//       round body vs ground plane              one per core end point (sphere 1, capsule 2)
+//       round body vs static box / free box     scene_sphere_box at each core end point with the radius (exact for a sphere); a capsule also at the
+//                                               point of its segment nearest to the box when that point is strictly inside the segment (the signed
+//                                               distance to a box is convex along a segment: 16 halvings on the sign of its derivative) -- a capsule
+//                                               lying across a knife edge
+//       round body vs round body                closest points of the two core segments, one contact; parallel capsules: two, at the ends of the overlap
+//       actor sphere vs free round body         closest point of the core segment to the sphere centre, one contact in the actor region
+//       box corner vs free round body           none: the round body's own test against the box is the exact one; the box-corner and static-corner
+//                                               loops, scene_box_edge and scene_face_crossings skip round bodies
+//     Stated approximations: capsule vs box is the two end spheres plus one interior point (a capsule lying along a box edge shorter than itself
+//     has no contact at the edge's ends); one contact per round pair.  Static bodies stay boxes.  oracle/scene.py knows boxes only: the round
+//     bodies' evidence is first principles (rolling, slipping, impacts: tests/test_scene_shapes.py) and the two backends against each other.
 //   * contact slots are data dependent: at most KARM actor contacts (taken in sphere order, grouped by actor body) and KBOX box contacts
 //     (box order, corner order, then ground / static boxes / free boxes); refusals are counted.
 //   * contacts are WARM STARTED although their slots are data dependent: a contact is identified by its feature (actor sphere x target, or box
@@ -41,7 +56,7 @@ constexpr int kSceneMaxFree = 4, kSceneMaxStatic = 4;
 struct SceneParams {        // mirrors MiScene (include/mi_engine.h)
     int n_free, n_static;
     int arm_gravity;        // 0: asset option disable_gravity on the articulated actor
-    int pad;
+    int free_shape;         // 4 bits per free body i, (free_shape >> 4 * i) & 15: 0 box, 1 sphere {r, r, r}, 2 capsule {half length, r, r} along local x
     float free_half[kSceneMaxFree][3], free_mass[kSceneMaxFree], free_inertia[kSceneMaxFree][3], free_mu[kSceneMaxFree];
     float free_init[kSceneMaxFree][7];      // start pose (create_actor): what reset leaves
     float static_pos[kSceneMaxStatic][3], static_quat[kSceneMaxStatic][4], static_half[kSceneMaxStatic][3], static_mu[kSceneMaxStatic];
@@ -224,7 +239,7 @@ template <class M>
 struct SceneSim : Sim<M> {
     using B = Sim<M>;
     static constexpr int NB = M::NB, ND = M::ND, NV = M::NV, OFF = M::OFF, NSPH = M::NSPH, NSENS = M::NSENS, NLIM = B::NLIM, NVA = B::NVA;
-    static_assert(M::FIXED == 1, "SceneSim: a fixed-base actor (the scene's free bodies are boxes)");
+    static_assert(M::FIXED == 1, "SceneSim: a fixed-base actor (the scene's free bodies are boxes, spheres and capsules)");
     static constexpr int KARM = 24, KBOX = 24;              // contact slots: actor spheres, box corners
     // the chain part of an actor contact's rows is stored DENSE over the actor's coordinates (zeros off the body's chain): the sweeps then visit the
     // actor slots in ONE loop with one copy of the contact code.  (Until round 6 the rows were packed along the body's chain and the sweeps went body
@@ -284,6 +299,8 @@ struct SceneSim : Sim<M> {
         auto lam = [&](int row) MI_LAMBDA -> float& { return rows(R_LIMG + 2 * NLIM + row); };
         const float invh = MI_RCP(h);
         const int nf = SP.n_free < kSceneMaxFree ? SP.n_free : kSceneMaxFree, ns = SP.n_static < kSceneMaxStatic ? SP.n_static : kSceneMaxStatic;
+        // shape of free body i: a scalar read of the kernel argument shifted by the body number (no run-time index into the struct, no LDS)
+        auto shape_of = [&](int i) MI_LAMBDA -> int { return (SP.free_shape >> (4 * i)) & 15; };
         typename B::Ctx c;
         float (&S)[M::NDA][6] = c.S;
         float (&L)[M::NM] = c.L;
@@ -468,6 +485,8 @@ struct SceneSim : Sim<M> {
                         float hb_[3];
                         ld3(fr_ ? W_HF : W_HS, ib, hb_);
                         scene_sphere_box(cl, rbound, hb_, &dist, nl);
+                        const int sh_ = fr_ ? shape_of(ib) : 0;
+                        if (sh_ != 0) dist = MI_SQRT(dot3(rel, rel)) - rbound - ((sh_ == 2 ? hb_[0] : 0.f) + hb_[1]);      // a round body's bounding radius
                         tmask |= (dist < P.contact_offset + 1e-4f) ? (1 << t) : 0;
                     }
                 }
@@ -493,6 +512,16 @@ struct SceneSim : Sim<M> {
                         float cl[3], nl[3], dist;
                         matTvec3(Rb_, rel, cl);
                         scene_sphere_box(cl, rad, hb_, &dist, nl);
+                        const int sh_ = fr_ ? shape_of(ib) : 0;
+                        if (sh_ != 0) {         // a round body: the sphere's centre against the nearest point of the core segment (local x)
+                            const float hl_ = (sh_ == 2) ? hb_[0] : 0.f;
+                            const float dl[3] = {cl[0] - fminf(fmaxf(cl[0], -hl_), hl_), cl[1], cl[2]};
+                            const float d2 = dot3(dl, dl);
+                            const float inv = MI_RSQ(fmaxf(d2, 1e-30f));
+                            const bool far_ = d2 > 1e-24f;
+                            dist = d2 * inv - rad - hb_[1];
+                            nl[0] = far_ ? dl[0] * inv : 0.f; nl[1] = far_ ? dl[1] * inv : 0.f; nl[2] = far_ ? dl[2] * inv : 1.f;
+                        }
                         if (!(dist < P.contact_offset)) continue;
                         if (cnt >= KARM) { refused += 1; continue; }
                         float fr[3][3], pc[3];
@@ -552,7 +581,8 @@ struct SceneSim : Sim<M> {
             ld3(W_XF, i, xi);
             float hi_[3];
             ld3(W_HF, i, hi_);
-            const float ri = MI_SQRT(dot3(hi_, hi_));
+            const int shi = shape_of(i);
+            const float ri = (shi != 0) ? ((shi == 2 ? hi_[0] : 0.f) + hi_[1]) : MI_SQRT(dot3(hi_, hi_));       // a round body: half length + radius
             for (int t = 0; t < ns + nf; ++t) {
                 const bool st_ = t < ns;
                 const int j = st_ ? t : t - ns;
@@ -562,11 +592,14 @@ struct SceneSim : Sim<M> {
                 float hj[3];
                 ld3(st_ ? W_HS : W_HF, j, hj);
                 const float d[3] = {xi[0] - xj[0], xi[1] - xj[1], xi[2] - xj[2]};
-                const float reach = ri + MI_SQRT(dot3(hj, hj)) + P.contact_offset + 1e-4f;
+                const int shj = st_ ? 0 : shape_of(j);
+                const float rj = (shj != 0) ? ((shj == 2 ? hj[0] : 0.f) + hj[1]) : MI_SQRT(dot3(hj, hj));
+                const float reach = ri + rj + P.contact_offset + 1e-4f;
                 pmask |= (dot3(d, d) < reach * reach) ? (1u << (i * NTGT + t)) : 0u;
             }
         }
         for (int i = 0; i < nf; ++i) {
+            if (shape_of(i) != 0) continue;         // (round bodies: below)
             float Ri[9], xi[3];
             ld9(W_RF, i, Ri);
             ld3(W_XF, i, xi);
@@ -578,7 +611,7 @@ struct SceneSim : Sim<M> {
                 matvec3(Ri, pl, pr);
                 sfor<3>([&](auto K) MI_LAMBDA { pc[K] = xi[K] + pr[K]; });
                 for (int t = -1; t < ns + nf; ++t) {
-                    if (t >= ns && t - ns == i) continue;
+                    if (t >= ns && (t - ns == i || shape_of(t - ns) != 0)) continue;
                     if (t >= 0 && !((pmask >> (i * NTGT + t)) & 1u)) continue;
                     float n[3], dist, mu_b;
                     int ib = -1;
@@ -658,7 +691,9 @@ struct SceneSim : Sim<M> {
         // the corners of the STATIC boxes inside free boxes (a plate lying on a stand smaller than itself has no corner of its own in the stand):
         // the free box is pushed back along the inward normal of the face the corner is nearest to
         constexpr int FID_SC = 1 + NSPH * NTGT + kSceneMaxFree * 8 * (NTGT + 1), FID_EE = FID_SC + kSceneMaxStatic * 8 * kSceneMaxFree,
-                      FID_FC = FID_EE + kSceneMaxFree * NTGT * 9;
+                      FID_FC = FID_EE + kSceneMaxFree * NTGT * 9, FID_RD = FID_FC + kSceneMaxFree * NTGT * 8,
+                      FID_END = FID_RD + kSceneMaxFree * (NTGT + 1) * 4;
+        static_assert(FID_END < (1 << 23), "feature ids are small positive integers (carried as the bit patterns of denormal floats: copied, never computed with)");
         for (int t = 0; t < ns; ++t) {
             float Rt[9], xt[3];
             ld9(W_RS, t, Rt);
@@ -671,6 +706,7 @@ struct SceneSim : Sim<M> {
                 matvec3(Rt, pl, pr);
                 sfor<3>([&](auto K) MI_LAMBDA { pc[K] = xt[K] + pr[K]; });
                 for (int j = 0; j < nf; ++j) {
+                    if (shape_of(j) != 0) continue;
                     if (!((pmask >> (j * NTGT + t)) & 1u)) continue;
                     float Rb_[9], xb_[3], cl[3], nl[3], n[3], dist;
                     ld9(W_RF, j, Rb_);
@@ -692,6 +728,7 @@ struct SceneSim : Sim<M> {
         // contact when the least-penetration axis is the cross product of an edge of each (scene_box_edge) --, or, when a face axis wins, the points
         // where the incident face's outline crosses the reference face's (scene_face_crossings)
         for (int i = 0; i < nf; ++i) {
+            if (shape_of(i) != 0) continue;
             float Ri[9], xi[3], hi_[3];
             ld9(W_RF, i, Ri);
             ld3(W_XF, i, xi);
@@ -699,6 +736,7 @@ struct SceneSim : Sim<M> {
             for (int t = 0; t < ns + nf - 1 - i; ++t) {
                 const bool st_ = t < ns;
                 const int j = st_ ? t : i + 1 + (t - ns);
+                if (!st_ && shape_of(j) != 0) continue;
                 if (!((pmask >> (i * NTGT + (st_ ? j : ns + j))) & 1u)) continue;
                 float Rb_[9], xb_[3], n_[3], pc_[3], dist_;
                 int axes;
@@ -725,6 +763,99 @@ struct SceneSim : Sim<M> {
                 };
                 if (ref_a) scene_face_crossings(Ri, xi, hi_, axes - 4, Rb_, xb_, hj, emit);
                 else scene_face_crossings(Rb_, xb_, hj, axes, Ri, xi, hi_, emit);
+            }
+        }
+        // ROUND bodies (spheres, capsules): core segment xi + s ax, |s| <= hl, radius r, against the ground plane (t = -1), the static boxes, the free
+        // boxes and the round bodies behind them; side A = the round body, contact point on its surface.  Point e of a target: 0, 1 the segment's
+        // ends (a sphere has one), 2 a capsule's interior point nearest to a box; against a round body 0 is the pair of closest points, 1 the second
+        // contact of parallel capsules.  The shape tests are scalar (kernel argument); every loop runs a fixed number of times.
+        for (int i = 0; i < nf; ++i) {
+            const int shi = shape_of(i);
+            if (shi == 0) continue;
+            float Ri[9], xi[3], hi_[3], ax[3];
+            ld9(W_RF, i, Ri);
+            ld3(W_XF, i, xi);
+            ld3(W_HF, i, hi_);
+            const float hl = (shi == 2) ? hi_[0] : 0.f, r = hi_[1];
+            sfor<3>([&](auto K) MI_LAMBDA { ax[K] = Ri[3 * K]; });
+            for (int t = -1; t < ns + nf; ++t) {
+                const bool st_ = t >= 0 && t < ns;
+                const int j = (t < ns) ? t : t - ns;
+                const int shj = (t >= ns) ? shape_of(j) : 0;
+                if (t >= ns && (j == i || (shj != 0 && j < i))) continue;          // a round pair belongs to its lower body
+                if (t >= 0 && !((pmask >> (i * NTGT + t)) & 1u)) continue;
+                float Rb_[9], xb_[3], hb_[3], c0[3] = {0.f, 0.f, 0.f}, al[3] = {0.f, 0.f, 0.f};
+                float sa0 = -hl, sa1 = hl, sb0 = 0.f, sb1 = 0.f, gl = 0.f, gh = 0.f, mu_b = P.plane_mu;
+                bool two = false;
+                if (t >= 0) {
+                    ld9(st_ ? W_RS : W_RF, j, Rb_);
+                    ld3(st_ ? W_XST : W_XF, j, xb_);
+                    ld3(st_ ? W_HS : W_HF, j, hb_);
+                    mu_b = st_ ? SP.static_mu[j] : SP.free_mu[j];
+                    const float rel[3] = {xi[0] - xb_[0], xi[1] - xb_[1], xi[2] - xb_[2]};
+                    if (shj == 0) {             // the segment in the box's frame
+                        matTvec3(Rb_, rel, c0);
+                        matTvec3(Rb_, ax, al);
+                    } else {                    // closest points of the two core segments: |rel + s ax - q w|^2 over |s| <= hl, |q| <= hq
+                        const float hq = (shj == 2) ? hb_[0] : 0.f;
+                        const float w_[3] = {Rb_[0], Rb_[3], Rb_[6]};
+                        const float b_ = dot3(ax, w_), c_ = dot3(ax, rel), f_ = dot3(w_, rel);
+                        const float den = 1.f - b_ * b_;
+                        float s_ = (den > 1e-6f) ? fminf(fmaxf((b_ * f_ - c_) * MI_RCP(fmaxf(den, 1e-6f)), -hl), hl) : 0.f;
+                        const float q_ = b_ * s_ + f_, qc = fminf(fmaxf(q_, -hq), hq);
+                        s_ = (qc != q_) ? fminf(fmaxf(b_ * qc - c_, -hl), hl) : s_;
+                        // parallel capsules: the overlap of the other segment's shadow [-c - hq, -c + hq] with the own one
+                        const float lo = fmaxf(-hl, -c_ - hq), up = fminf(hl, -c_ + hq);
+                        two = !(den > 1e-6f) && (up > lo + 1e-6f);
+                        sa0 = two ? lo : s_; sa1 = up;
+                        sb0 = two ? fminf(fmaxf(b_ * lo + f_, -hq), hq) : qc; sb1 = fminf(fmaxf(b_ * up + f_, -hq), hq);
+                    }
+                }
+                for (int e = 0; e < 3; ++e) {
+                    if (e == 1 && shi != 2) continue;
+                    if (e == 2 && (shi != 2 || t < 0 || shj != 0)) continue;
+                    float s_ = (e == 0) ? sa0 : sa1, n[3], pa[3], dist;
+                    bool ok = true;
+                    if (e == 2) {               // the interior minimum of a convex function: halve on the sign of its derivative n . ax
+                        float lo = -hl, up = hl;
+                        for (int it = 0; it < 16; ++it) {
+                            const float sm = 0.5f * (lo + up);
+                            const float pl[3] = {c0[0] + sm * al[0], c0[1] + sm * al[1], c0[2] + sm * al[2]};
+                            float nl[3], d_;
+                            scene_sphere_box(pl, r, hb_, &d_, nl);
+                            const bool dn = dot3(nl, al) > 0.f;
+                            up = dn ? sm : up; lo = dn ? lo : sm;
+                        }
+                        s_ = 0.5f * (lo + up);
+                        ok = (gl < -1e-4f) && (gh > 1e-4f);         // strictly inside: the distance falls from both ends
+                    }
+                    sfor<3>([&](auto K) MI_LAMBDA { pa[K] = xi[K] + s_ * ax[K]; });
+                    if (t < 0) {
+                        n[0] = 0.f; n[1] = 0.f; n[2] = 1.f;
+                        dist = (root[2] + pa[2]) - r - P.ground_z;
+                    } else if (shj == 0) {
+                        const float pl[3] = {c0[0] + s_ * al[0], c0[1] + s_ * al[1], c0[2] + s_ * al[2]};
+                        float nl[3];
+                        scene_sphere_box(pl, r, hb_, &dist, nl);
+                        matvec3(Rb_, nl, n);
+                        const float g_ = dot3(nl, al);
+                        gl = (e == 0) ? g_ : gl; gh = (e == 1) ? g_ : gh;
+                    } else {
+                        const float q_ = (e == 0) ? sb0 : sb1;
+                        ok = (e == 0) || two;
+                        const float d[3] = {pa[0] - (xb_[0] + q_ * Rb_[0]), pa[1] - (xb_[1] + q_ * Rb_[3]), pa[2] - (xb_[2] + q_ * Rb_[6])};
+                        const float d2 = dot3(d, d);
+                        const float inv = MI_RSQ(fmaxf(d2, 1e-30f));
+                        const bool far_ = d2 > 1e-24f;
+                        dist = d2 * inv - r - hb_[1];
+                        n[0] = far_ ? d[0] * inv : 0.f; n[1] = far_ ? d[1] * inv : 0.f; n[2] = far_ ? d[2] * inv : 1.f;
+                    }
+                    if (!ok || !(dist < P.contact_offset)) continue;
+                    if (nbox >= KBOX) { refused += 1; continue; }
+                    const float pc[3] = {pa[0] - r * n[0], pa[1] - r * n[1], pa[2] - r * n[2]};
+                    const int tt = (t < 0) ? 0 : (st_ ? 1 + j : 1 + kSceneMaxStatic + j);
+                    add_box_contact(i, (t >= ns) ? j : -1, n, pc, dist, 0.5f * (SP.free_mu[i] + mu_b), FID_RD + ((i * (NTGT + 1) + tt) * 4 + e));
+                }
             }
         }
         *ncontact = (narm + nbox) | (refused << 16);

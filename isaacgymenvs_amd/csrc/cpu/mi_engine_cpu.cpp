@@ -76,7 +76,15 @@ extern "C" int mi_engine_create(const char* task, const MiSimParams* sim, const 
     else if (t == T_ANYMAL) memcpy(&e->anymal, task_params, sizeof(AnymalParams));
     else if (t == T_ANYMAL_FLAT) memcpy(&e->anymal_flat, task_params, sizeof(AnymalFlatParams));
     else if (is_hand_task(t)) memcpy(&e->hand, task_params, sizeof(HandParams));
-    else if (t == T_ARTICULATION) memcpy(e->artic, task_params, sizeof(MiArticulationParams));
+    else if (t == T_ARTICULATION) {
+        memcpy(e->artic, task_params, sizeof(MiArticulationParams));
+        const MiScene& sc = ((const MiArticulationParams*)task_params)->scene;       // the check of mi_engine.hip
+        for (int i = 0; i < sc.n_free && i < MI_SCENE_MAX_FREE; ++i)
+            if (((sc.free_shape >> (4 * i)) & 15) > MI_SHAPE_CAPSULE) {
+                delete e;
+                return fail("mi_engine_create: MiScene.free_shape holds an unknown shape code (0 box, 1 sphere, 2 capsule)");
+            }
+    }
     else memcpy(&e->loco, task_params, sizeof(LocoParams));
     memset(&e->terrain, 0, sizeof(e->terrain));
     e->terrain.walls = 1;

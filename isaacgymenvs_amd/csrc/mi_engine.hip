@@ -332,7 +332,13 @@ extern "C" int mi_engine_create(const char* task, const MiSimParams* sim, const 
         }
     }
     else if (is_hand_task(t)) memcpy(&e->hand, task_params, sizeof(HandParams));
-    else if (t == T_ARTICULATION) memcpy(&e->artic, task_params, sizeof(ArticulationParams));
+    else if (t == T_ARTICULATION) {
+        memcpy(&e->artic, task_params, sizeof(ArticulationParams));
+        if (!scene_shapes_known(e->artic.scene.n_free, e->artic.scene.free_shape)) {
+            delete e;
+            return fail("mi_engine_create: MiScene.free_shape holds an unknown shape code (0 box, 1 sphere, 2 capsule)");
+        }
+    }
     else memcpy(&e->loco, task_params, sizeof(LocoParams));
     Layout L;
     memset(&e->v, 0, sizeof(View));

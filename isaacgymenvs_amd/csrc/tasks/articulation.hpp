@@ -23,6 +23,11 @@ struct ArticulationParams {   // mirrors MiArticulationParams (include/mi_engine
 // [slot][lane], host: a per-env array); warm: last sub-step's (feature, impulses) per contact slot, read and rewritten (device: staged in LDS by the
 // kernel, host: the tensor itself).
 static inline bool articulation_has_scene(const ArticulationParams& p) { return p.scene.n_free + p.scene.n_static > 0; }
+// mi_engine_create's check of MiScene.free_shape: every free body's code is a known shape (0 box, 1 sphere, 2 capsule)
+static inline bool scene_shapes_known(const int n_free, const int free_shape) {
+    for (int i = 0; i < n_free && i < kSceneMaxFree; ++i) if (((free_shape >> (4 * i)) & 15) > 2) return false;
+    return true;
+}
 // floats of the scene form's row store (1 for a floating-base robot, which has no scene form: SceneSim<M> is never instantiated for it)
 template <class M, bool F = (M::FIXED == 1)> struct SceneRows { static constexpr int value = 1; };
 template <class M> struct SceneRows<M, true> { static constexpr int value = SceneSim<M>::ROW_SLOTS; };

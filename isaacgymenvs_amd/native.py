@@ -147,11 +147,13 @@ class MiBallBalanceParams(C.Structure):
 
 
 MI_SCENE_MAX_FREE, MI_SCENE_MAX_STATIC = 4, 4
+MI_SHAPE_BOX, MI_SHAPE_SPHERE, MI_SHAPE_CAPSULE = 0, 1, 2
 
 
 class MiScene(C.Structure):
-    """include/mi_engine.h MiScene: the free / static boxes beside a fixed-base articulated actor (csrc/core/scene_engine.hpp)"""
-    _fields_ = [("n_free", C.c_int32), ("n_static", C.c_int32), ("arm_gravity", C.c_int32), ("pad", C.c_int32),
+    """include/mi_engine.h MiScene: the free bodies (free_shape: 4 bits each, MI_SHAPE_*) / static boxes beside a fixed-base articulated actor
+    (csrc/core/scene_engine.hpp)"""
+    _fields_ = [("n_free", C.c_int32), ("n_static", C.c_int32), ("arm_gravity", C.c_int32), ("free_shape", C.c_int32),
                 ("free_half", (C.c_float * 3) * MI_SCENE_MAX_FREE), ("free_mass", C.c_float * MI_SCENE_MAX_FREE),
                 ("free_inertia", (C.c_float * 3) * MI_SCENE_MAX_FREE), ("free_mu", C.c_float * MI_SCENE_MAX_FREE),
                 ("free_init", (C.c_float * 7) * MI_SCENE_MAX_FREE),

@@ -213,9 +213,15 @@ class RigidShapeProperties(_Scalars):
         super().__init__(friction=friction, rolling_friction=0.0, torsion_friction=0.0, restitution=0.0, compliance=0.0, thickness=0.0)
 
 
+class Mat33:
+    """rows x, y, z (gymapi.Mat33): the inertia of a rigid body in its own frame"""
+    def __init__(self, x=None, y=None, z=None):
+        self.x, self.y, self.z = x or Vec3(), y or Vec3(), z or Vec3()
+
+
 class RigidBodyProperties(_Scalars):
-    def __init__(self, mass=0.0):
-        super().__init__(mass=mass, invMass=(1.0 / mass if mass > 0 else 0.0), com=Vec3(), inertia=None)
+    def __init__(self, mass=0.0, inertia=None):
+        super().__init__(mass=mass, invMass=(1.0 / mass if mass > 0 else 0.0), com=Vec3(), inertia=inertia)
 
 
 class TendonProperties(_Scalars):
@@ -331,6 +337,28 @@ def _single_box_urdf(path):
             inertia = [float(it.get(k)) for k in ("ixx", "iyy", "izz")]
     return dict(link=ln.get("name"), dims=[float(d) for d in dims], pos=[float(x) for x in pos], quat=[float(x) for x in quat],
                 mass=mass if (mass is not None and mass > 0) else None, inertia=inertia, mesh=mesh, hollow=hollow)
+
+
+def _scene_body(a):
+    """a free body of a scene (gym.create_box / create_sphere / create_capsule, or a one-body box URDF): -> shape code (include/mi_engine.h
+    MI_SHAPE_*), half sizes (MiScene.free_half), mass, principal inertias of the solid.  Mass: the file's <inertial> if it has one, else asset
+    option density x volume.  The capsule's axis is its local x."""
+    dens = float(getattr(a.options, "density", 1000.0) or 1000.0)
+    if a.object_type == "sphere":
+        r = a.dims[0]
+        m = dens * 4.0 / 3.0 * np.pi * r ** 3
+        return 1, [r, r, r], m, [0.4 * m * r * r] * 3
+    if a.object_type == "capsule":
+        r, ln = a.dims[0], a.dims[1]
+        mc, ms = dens * np.pi * r * r * ln, dens * 4.0 / 3.0 * np.pi * r ** 3           # the cylinder, the two hemispheres together
+        # across the axis: the cylinder's own + each hemisphere's about its centre of mass (83/320 m r^2), carried to the capsule's centre
+        # (parallel axes, 3 r / 8 beyond the cylinder's end): together m_s (2/5 r^2 + l^2 / 4 + 3 l r / 8)
+        across = mc * (ln * ln / 12.0 + r * r / 4.0) + ms * (0.4 * r * r + ln * ln / 4.0 + 0.375 * ln * r)
+        return 2, [0.5 * ln, r, r], mc + ms, [0.5 * mc * r * r + 0.4 * ms * r * r, across, across]
+    d = a.dims
+    m = float(a.mass) if getattr(a, "mass", None) else dens * d[0] * d[1] * d[2]      # (a URDF's <inertial> wins over the density)
+    ine = list(a.inertia) if getattr(a, "inertia", None) else [m * (d[(c + 1) % 3] ** 2 + d[(c + 2) % 3] ** 2) / 12.0 for c in range(3)]
+    return 0, [0.5 * x for x in d], m, ine
 
 
 class _Asset:
@@ -778,6 +806,8 @@ class Gym:
             # a box actor of a scene (create_box or a one-body URDF): the file's <inertial> mass, else density x volume (prepare_sim's rule)
             dens = float(getattr(a.options, "density", 1000.0) or 1000.0)
             return np.array([float(a.mass) if getattr(a, "mass", None) else dens * a.dims[0] * a.dims[1] * a.dims[2]])
+        if a.spec is None and a.object_type in ("sphere", "capsule") and getattr(sim, "scene", None) and actor in sim.scene:
+            return np.array([_scene_body(a)[2]])            # a round body of a scene: density x volume
         if a.spec is None:
             return np.array([_object_mass(a.object_type, sim.asset.task if sim.slots and any(sl["asset"].spec is not None for sl in sim.slots) else "ShadowHand")])
         return np.asarray([float(a.spec.mass[int(d)]) for d in a.body_dyn])
@@ -792,6 +822,10 @@ class Gym:
                 m = m * sim.props.body[env.index][np.asarray(a.body_dyn, int)]
             elif actor == [k for k, sl in enumerate(sim.slots) if sl["asset"].spec is None][0]:
                 m = m * sim.props.obj_mass[env.index]
+        if a.spec is None and getattr(sim, "scene", None) and sim.scene.get(actor, ("", 0))[0] == "free":
+            # a free body of a scene: its principal inertias (the solid's, along the body axes) as the engine holds them
+            ine = _scene_body(a)[3]
+            return [RigidBodyProperties(float(m[0]), Mat33(Vec3(ine[0], 0.0, 0.0), Vec3(0.0, ine[1], 0.0), Vec3(0.0, 0.0, ine[2])))]
         return [RigidBodyProperties(float(x)) for x in m]
 
     def set_actor_rigid_body_properties(self, env, actor, props, recompute_inertia=False):
@@ -1096,8 +1130,10 @@ class Gym:
                 from ...assets.model import quat_mul, quat_to_mat
                 for k, sl in boxes:
                     a = sl["asset"]
-                    if a.object_type != "box":
-                        raise NotImplementedError(f"scene actors are gym.create_box assets (got a {a.object_type})")
+                    if a.object_type not in ("box", "sphere", "capsule"):
+                        raise NotImplementedError(f"scene actors are gym.create_box / create_sphere / create_capsule assets (got a {a.object_type})")
+                    if a.object_type != "box" and bool(getattr(a.options, "fix_base_link", False)):
+                        raise NotImplementedError(f"the static bodies of a scene are boxes (got a {a.object_type} with fix_base_link): spheres and capsules are free bodies")
                     g_r, g_k = rslot.get("group", -1), sl.get("group", -1)
                     if getattr(a, "hollow", False):
                         continue       # a ring wall without a collision shape (load_asset warned): lives in the stand-in
@@ -1114,7 +1150,7 @@ class Gym:
                             ps[e_, 3:7] = quat_mul(ps[e_, 3:7], off_q)
                     if fixed and np.abs(ps - ps[0]).max() > 1e-9:
                         raise NotImplementedError("a static box of the scene stands at the same env-local pose in every env")
-                    half = [0.5 * d for d in a.dims]
+                    shape, half, m, ine = _scene_body(a)
                     mu = float(sl["friction"].get(0, 1.0)) if sl["friction"] else 1.0
                     if fixed:
                         j = sc.n_static
@@ -1130,14 +1166,11 @@ class Gym:
                     else:
                         j = sc.n_free
                         if j >= native.MI_SCENE_MAX_FREE:
-                            raise NotImplementedError(f"a scene holds at most {native.MI_SCENE_MAX_FREE} free boxes")
-                        dens = float(getattr(a.options, "density", 1000.0) or 1000.0)
-                        m = float(a.mass) if getattr(a, "mass", None) else dens * a.dims[0] * a.dims[1] * a.dims[2]      # (a URDF's <inertial> wins over the density)
+                            raise NotImplementedError(f"a scene holds at most {native.MI_SCENE_MAX_FREE} free bodies")
                         sc.free_mass[j], sc.free_mu[j] = m, mu
+                        sc.free_shape |= shape << (4 * j)
                         for c in range(3):
-                            o1, o2 = a.dims[(c + 1) % 3], a.dims[(c + 2) % 3]
-                            ine = a.inertia[c] if getattr(a, "inertia", None) else m * (o1 * o1 + o2 * o2) / 12.0
-                            sc.free_half[j][c], sc.free_inertia[j][c] = float(half[c]), float(ine)
+                            sc.free_half[j][c], sc.free_inertia[j][c] = float(half[c]), float(ine[c])
                         for c in range(7):
                             sc.free_init[j][c] = float(ps[0, c])
                         sim.scene[k] = ("free", j)

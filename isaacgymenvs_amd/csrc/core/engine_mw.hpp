@@ -119,7 +119,10 @@ struct SimMW : Sim<M> {
     // loads issued by the caller), 2: already IN the row store, left there by the previous sub-step of the same launch (KEEP).
     // KEEP: leave the signed limit impulses in the row store for a following sub-step of the same launch (mw_kernels.hpp, fused sub-steps);
     // the contact impulses are there anyway.
-    template <int R, bool KEEP = false, int RS, class GND, class BAR>
+    // SENS: also leave the force-sensor values of the own bodies (the very floats stored to `sensor`) in sens_own, for a post step that runs
+    // on the same wave (mw_kernels.hpp loco_post_role) and would otherwise read them straight back from memory.
+    float sens_own[6 * M::NSENSA];      // written with SENS only; entries of other roles' sensors are never set
+    template <int R, bool KEEP = false, bool SENS = false, int RS, class GND, class BAR>
     MI_HD void substep_role(const SimParams& P, const float* tau, const float h, const RowStore<RS> rows, const Strided lamc,
                             const Strided laml, const Strided sensor, const Strided dof_force, const GND& gnd, const float mu_env,
                             const Strided netf, const int stage, const BAR& bar) {
@@ -584,7 +587,10 @@ struct SimMW : Sim<M> {
             if constexpr (owns_body<R>(B_)) sfor<3>([&](auto K) MI_LAMBDA { netf(3 * B_ + K) = nf[B_][K]; });
         });
         sfor<NSENS>([&](auto K_) MI_LAMBDA {
-            if constexpr (owns_body<R>(M::sens_body[K_])) sfor<6>([&](auto C) MI_LAMBDA { sensor(6 * K_ + C) = sens[6 * K_ + C]; });
+            if constexpr (owns_body<R>(M::sens_body[K_])) sfor<6>([&](auto C) MI_LAMBDA {
+                sensor(6 * K_ + C) = sens[6 * K_ + C];
+                if constexpr (SENS) sens_own[6 * K_ + C] = sens[6 * K_ + C];
+            });
         });
         MI_PHASE();
         sfor<ND>([&](auto D) MI_LAMBDA {

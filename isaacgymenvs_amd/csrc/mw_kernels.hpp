@@ -1,6 +1,7 @@
 // mw_kernels.hpp -- the multi-wave physics sub-step kernel (core/engine_mw.hpp) and its launcher.  Included only by the
 // kernels_mw_<model>.hip translation units, which instantiate launch_substeps_mw for one model / ground pair each.
 #pragma once
+#include <cstddef>
 #include "step_kernels.hpp"
 #include "core/engine_mw.hpp"
 #include "tasks/anymal_step.hpp"      // anymal_netf_norm, anymal_knee_body: the AnymalTerrain launch's curriculum tail (mw_role_fused)
@@ -152,10 +153,28 @@ struct MwFusedPostArgs {
     MwFusedArgs<GND> f;
     LocoParams tp;
 };
+// Kernel arguments read through the kernarg segment pointer are fetched where they are first used, one scalar-cache line at a time, and every launch
+// gets a fresh argument buffer: the first touch of a line is a miss, paid on the spot.  The part of the arguments that only the post step reads
+// would be missed behind the last sub-step, on the critical wave.  KernargLines issues one scalar load per 64-byte line of bytes [BEGIN, END) of
+// the argument struct (and of its last dword, should the buffer not be line aligned) where it is constructed -- at kernel entry, next to the load of
+// N, so that the misses overlap -- and drop() gives the loaded words up at the wait that load has anyway: no SGPR stays live behind it.
+template <size_t BEGIN, size_t END>
+struct KernargLines {
+    static_assert(BEGIN % 4 == 0 && END % 4 == 0 && BEGIN < END, "dword-aligned byte range of the argument struct");
+    static constexpr int NL = (int)((END - BEGIN + 63) / 64) + 1;
+    uint32_t x[NL];
+    __device__ __forceinline__ explicit KernargLines(const void* args) {
+        const uint32_t* p = static_cast<const uint32_t*>(args);
+        sfor<NL - 1>([&](auto K) MI_LAMBDA { x[K] = p[(BEGIN + 64 * K) / 4]; });
+        x[NL - 1] = p[END / 4 - 1];
+    }
+    __device__ __forceinline__ void drop() const { sfor<NL>([&](auto K) MI_LAMBDA { asm volatile("" ::"s"(x[K])); }); }
+};
 // S: the role's simulator (SimMW<M>; SimMWC<M> for the Humanoid, whose launch is its LAST sub-step's: mwc_kernels.hpp).  act: the clamped actions in
 // the role's registers, or nullptr -- then they are read back from v.actions (stored by the step's first launch).  BAR_FIRST: a barrier before
-// anything is written to xpost (an area some role may still be reading in its output phase).
-template <class S, class M, bool HUM, int E, int R, bool BAR_FIRST = false>
+// anything is written to xpost (an area some role may still be reading in its output phase).  SENS_REG: the force-sensor values of the own bodies
+// are in sim.sens_own (left there by the last sub-step's P5, substep_role<R, KEEP, SENS>); otherwise they are read back from v.sensor.
+template <class S, class M, bool HUM, int E, int R, bool BAR_FIRST = false, bool SENS_REG = false>
 __device__ __forceinline__ void loco_post_role(const View& v, const LocoParams& tp, S& sim, const float* act, const int e, float* xpost) {
     using T = Loco<M::ND, 6 * M::NSENS, HUM>;
     constexpr int ND = M::ND, NOBS = T::NOBS;
@@ -164,6 +183,11 @@ __device__ __forceinline__ void loco_post_role(const View& v, const LocoParams& 
     const uint32_t genv = (uint32_t)(v.env_offset + e);
     const bool do_reset = v.reset[e] != 0;
     int ep = v.episode[e];
+    // trunk role: every per-env scalar its part below reads, loaded here in one group with the two above (whose wait is here anyway): behind the
+    // stores of the post step each of these loads would be a round trip of its own on the one wave the workgroup is still waiting for
+    long long progress = 0, randomize = 0;
+    float potentials = 0.f, ep_ret = 0.f;
+    if constexpr (R == M::TRUNK_ROLE) { progress = v.progress[e] + 1; potentials = v.potentials[e]; ep_ret = v.ep_ret[e]; randomize = v.randomize[e]; }
     float* ob = v.obs + (size_t)e * NOBS;
     float* oc = v.obs_out + ((size_t)v.ring * N + e) * NOBS;
     const float c = v.clip_obs;
@@ -191,17 +215,22 @@ __device__ __forceinline__ void loco_post_role(const View& v, const LocoParams& 
             xpost[(3 * d + 0) * E] = one.actions; xpost[(3 * d + 1) * E] = one.electricity; xpost[(3 * d + 2) * E] = one.at_limit;
         }
     });
-    // ---- own force sensors (stored by this wave's P5; a load after the own store of the same address sees it)
+    // ---- own force sensors: the values P5 stored, from the registers it left them in; or read back (stored by this wave's P5: a load after the
+    // own store of the same address sees it) -- all six before the first put, whose stores the loads behind it would have to wait for
     sfor<M::NSENS>([&](auto K_) MI_LAMBDA {
         constexpr int k = K_;
-        if constexpr (S::template owns_body<R>(M::sens_body[k]))
-            sfor<6>([&](auto J) MI_LAMBDA { put(T::COL_SENS + 6 * k + J, v.sensor[(6 * k + J) * N + e] * tp.contact_force_scale); });
+        if constexpr (S::template owns_body<R>(M::sens_body[k])) {
+            float sv[6];
+            sfor<6>([&](auto J) MI_LAMBDA {
+                if constexpr (SENS_REG) sv[J] = sim.sens_own[6 * k + J]; else sv[J] = v.sensor[(6 * k + J) * N + e];
+            });
+            sfor<6>([&](auto J) MI_LAMBDA { put(T::COL_SENS + 6 * k + J, sv[J] * tp.contact_force_scale); });
+        }
     });
     if (do_reset) sfor<3 * M::NSPH>([&](auto K) MI_LAMBDA { if constexpr (S::template owns_body<R>(M::sph_body[K / 3])) v.lamc[K * N + e] = 0.f; });
     if constexpr (R != M::TRUNK_ROLE) { __syncthreads(); return; }
     // ---- trunk role: root part, reward, flags
-    long long progress = v.progress[e] + 1;
-    float potentials = v.potentials[e], prev_potentials;
+    float prev_potentials;
     if (do_reset) {
         float init_root[13];
         sfor<13>([&](auto K) MI_LAMBDA { init_root[K] = v.init_root[K * N + e]; sim.root[K] = init_root[K]; });
@@ -228,8 +257,8 @@ __device__ __forceinline__ void loco_post_role(const View& v, const LocoParams& 
     float rew;
     long long reset;
     T::reward_total(tp, o12[0], o12[10], o12[11], sm, 0LL, progress, potentials, prev_potentials, &rew, &reset);
-    episode_stats<E, true>(v, e, true, rew, reset, progress);
-    v.randomize[e] += 1;
+    episode_stats<E, true>(v, e, true, rew, reset, progress, ep_ret);
+    v.randomize[e] = randomize + 1;
     v.episode[e] = ep;
     v.potentials[e] = potentials;
     v.prev_potentials[e] = prev_potentials;
@@ -321,7 +350,7 @@ __device__ __forceinline__ void mw_role_fused(const MwFusedArgs<GND>& a, float* 
 #if defined(MI_TIMING)
         sim.tstamp = (tstamp != nullptr && i < 3) ? tstamp + 8 * i : nullptr;
 #endif
-        sim.template substep_role<R, true>(a.P, tau, h, RowStore<E>{lds_rows + lane}, lamc, laml, sensor, dof_force, a.gnd, mu_env, netf,
+        sim.template substep_role<R, true, POST>(a.P, tau, h, RowStore<E>{lds_rows + lane}, lamc, laml, sensor, dof_force, a.gnd, mu_env, netf,
                                            i == 0 ? 1 : 2, DevBarrier{});
         if constexpr (GND::HEIGHTFIELD) {
             if (i == a.n_sub - a.tail - 1 && v.dof_api != nullptr)       // (uniform) the task's refresh_dof_state_tensor at the end of its decimation loop
@@ -352,7 +381,7 @@ __device__ __forceinline__ void mw_role_fused(const MwFusedArgs<GND>& a, float* 
     }
     if constexpr (POST) {
         static_assert(3 * M::ND <= 16 * S::NLR, "the reward terms fit the (by now dead) tree-pass exchange area");
-        loco_post_role<S, M, HUM, E, R>(v, *tp, sim, act, e, lds_rows + (size_t)S::X_LR * E + lane);
+        loco_post_role<S, M, HUM, E, R, false, true>(v, *tp, sim, act, e, lds_rows + (size_t)S::X_LR * E + lane);
         MI_STAMP(31);
         return;
     }
@@ -375,8 +404,15 @@ __global__ __launch_bounds__(64 * M::NROLE, E == 8 ? 2 : 1) void substep_mw_fuse
     const MwFusedPostArgs<GND>& a = *reinterpret_cast<const MwFusedPostArgs<GND>*>(__builtin_amdgcn_kernarg_segment_ptr());
     const int lane = threadIdx.x;
     if (lane >= E) return;
+    // what only the post step reads: the View's pointers from `potentials` to `stats`, and the task parameters
+    const KernargLines<offsetof(MwFusedPostArgs<GND>, f.v.potentials), offsetof(MwFusedPostArgs<GND>, f.v.stats) + sizeof(float*)> view_tail(&a);
+    const KernargLines<offsetof(MwFusedPostArgs<GND>, tp), sizeof(MwFusedPostArgs<GND>)> task_params(&a);
+    const int N = a.f.v.N;
+    asm volatile("" ::"s"(N));           // (N loaded in the same group, waited for together)
+    view_tail.drop();
+    task_params.drop();
     const int e = xcd_env_base<E>(blockIdx.x) + lane;
-    if (e >= a.f.v.N) return;
+    if (e >= N) return;
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.y);
     switch (role) {
         case 0: mw_role_fused<M, GND, E, 0, true, HUM>(a.f, lds_rows, e, lane, &a.tp); break;

@@ -73,11 +73,12 @@ __device__ __forceinline__ float wave_sum_live(float v) {
 // job statistics: fire-and-forget hardware float atomics (global_atomic_add_f32).  Plain atomicAdd(float*) compiles to a compare-and-swap loop
 // here; every wave of a post kernel adds to the same five words, so the loops of 64-256 waves collided and retried.
 __device__ __forceinline__ void stat_add(float* p, float x) { unsafeAtomicAdd(p, x); }
+// ep_ret: the env's running return as the caller loaded it (v.ep_ret[e]; only read where `valid`)
 template <int ACTIVE = 64, bool LIVE_MASK = false>
-__device__ __forceinline__ void episode_stats(const View& v, int e, bool valid, float rew, long long reset, long long progress) {
+__device__ __forceinline__ void episode_stats(const View& v, int e, bool valid, float rew, long long reset, long long progress, float ep_ret) {
     float ret = 0.f, fin_ret = 0.f, fin_len = 0.f, fin = 0.f, r = 0.f, cnt = 0.f;
     if (valid) {
-        ret = v.ep_ret[e] + rew;
+        ret = ep_ret + rew;
         r = rew; cnt = 1.f;
         if (reset != 0) { fin_ret = ret; fin_len = (float)(progress + 1); fin = 1.f; ret = 0.f; }
         v.ep_ret[e] = ret;
@@ -93,6 +94,10 @@ __device__ __forceinline__ void episode_stats(const View& v, int e, bool valid, 
         stat_add(v.stats + 3, r);
         stat_add(v.stats + 4, cnt);
     }
+}
+template <int ACTIVE = 64, bool LIVE_MASK = false>
+__device__ __forceinline__ void episode_stats(const View& v, int e, bool valid, float rew, long long reset, long long progress) {
+    episode_stats<ACTIVE, LIVE_MASK>(v, e, valid, rew, reset, progress, valid ? v.ep_ret[e] : 0.f);
 }
 
 // ------------------------------------------------------------------------------------------------ physics sub-step

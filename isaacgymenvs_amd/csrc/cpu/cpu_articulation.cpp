@@ -10,7 +10,7 @@ static_assert(sizeof(MiArticulationParams) == sizeof(ArticulationParams), "MiArt
 ArticulationMeta mi_articulation_meta() { return ArticulationMeta{AM::ND, AM::NB, AM::NSENS, AM::NSPH, AM::FIXED}; }
 
 int cpu_articulation_reset(MiEngine* e, const int64_t* ids, int n) {
-    const ArticulationParams& p = *reinterpret_cast<const ArticulationParams*>(e->artic);
+    const ArticulationParams& p = e->artic;
     if (!ids) { for (int en = 0; en < e->v.N; ++en) articulation_reset_env<AM>(e->v, p, en); return 0; }
     for (int i = 0; i < n; ++i) if (ids[i] >= 0 && ids[i] < e->v.N) articulation_reset_env<AM>(e->v, p, (int)ids[i]);
     return 0;
@@ -32,7 +32,7 @@ static int scene_simulate(MiEngine* e, const ArticulationParams& p) {
 }
 int cpu_articulation_simulate(MiEngine* e) {
     const View& v = e->v;
-    const ArticulationParams& p = *reinterpret_cast<const ArticulationParams*>(e->artic);
+    const ArticulationParams& p = e->artic;
     if (articulation_has_scene(p)) return scene_simulate<AM>(e, p);     // free / static boxes beside the actor (core/scene_engine.hpp)
 #pragma omp parallel for schedule(static) num_threads(e->num_threads)
     for (int en = 0; en < v.N; ++en) {

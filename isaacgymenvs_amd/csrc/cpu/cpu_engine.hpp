@@ -1,6 +1,7 @@
-// cpu_engine.hpp -- what the translation units of the CPU backend share: the engine object and the per-thread statistics accumulators.
+// cpu_engine.hpp -- what the translation units of the CPU backend share: the engine object (the lifecycle core of csrc/engine_core.hpp plus what
+// only this backend has) and the per-thread statistics accumulators.
 // (cpu/mi_engine_cpu.cpp: C ABI + Cartpole / Ant / Humanoid / Quadcopter / Ingenuity / BallBalance; cpu/cpu_anymal.cpp: AnymalTerrain, Anymal;
-//  cpu/cpu_hand.cpp, compiled once per hand and object shape: ShadowHand, AllegroHand.)
+//  cpu/cpu_articulation.cpp: the run-time robot; cpu/cpu_hand.cpp, compiled once per hand and object shape: ShadowHand, AllegroHand.)
 #pragma once
 #include <omp.h>
 
@@ -12,41 +13,14 @@
 #include <vector>
 
 #include "../core/engine.hpp"
-#include "../arena_layout.hpp"
-#include "../task_views.hpp"
-#include "../tasks/shadow_hand.hpp"
+#include "../engine_core.hpp"
 
 using namespace mi;
 
-struct MiEngine {
-    int task, N;
-    SimParams P;
-    LocoParams loco;
-    CartpoleParams cart;
-    QuadcopterParams quad;
-    IngenuityParams ing;
-    BallBalanceParams bbot;
-    AnymalParams anymal;
-    AnymalFlatParams anymal_flat;
-    HandParams hand;
-    float artic[(sizeof(MiArticulationParams) + 3) / 4];    // ArticulationParams (csrc/tasks/articulation.hpp), opaque outside cpu_articulation.cpp
-    QuadView qv;
-    IngenuityView iv;
-    BbotView bv;
-    HandView hv;
-    AnymalTerrainDesc terrain;          // points into the two vectors below (mi_engine_set_terrain copies the caller's arrays)
-    std::vector<short> terrain_hs;
+struct MiEngine : EngineCore {
+    int num_threads;                    // sim.physx.num_threads: OpenMP threads over envs
+    std::vector<short> terrain_hs;      // mi_engine_set_terrain copies the caller's arrays: `terrain` points into these two
     std::vector<float> terrain_origins;
-    int max_init_level;
-    View v;
-    float clip_obs;
-    int control_freq_inv, num_threads;
-    std::vector<MiTensorDesc> descs;
-    unsigned long long steps;
-    float* lamp_arena;
-    float* dof_api_arena;
-    float* actor_scale_arena;   // the `actor_params` tensors: read by the sub-step once option "actor_tensors" is on (as in mi_engine.hip)
-    float* limit_shift_arena;
 };
 
 // job statistics (View::stats) of one OpenMP thread; added up in thread order after the loop over envs

@@ -17,228 +17,58 @@
 #include "cpu_hand.hpp"
 #include "../core/bbot_engine.hpp"
 
-static_assert(sizeof(MiSimParams) == sizeof(SimParams), "MiSimParams layout");
-static_assert(sizeof(MiLocoParams) == sizeof(LocoParams), "MiLocoParams layout");
-static_assert(sizeof(MiCartpoleParams) == sizeof(CartpoleParams), "MiCartpoleParams layout");
-static_assert(sizeof(MiQuadcopterParams) == sizeof(QuadcopterParams), "MiQuadcopterParams layout");
-static_assert(sizeof(MiIngenuityParams) == sizeof(IngenuityParams), "MiIngenuityParams layout");
-static_assert(sizeof(MiBallBalanceParams) == sizeof(BallBalanceParams), "MiBallBalanceParams layout");
-static_assert(sizeof(MiAnymalParams) == sizeof(AnymalParams), "MiAnymalParams layout");
-static_assert(sizeof(MiAnymalFlatParams) == sizeof(AnymalFlatParams), "MiAnymalFlatParams layout");
-static_assert(sizeof(MiHandRewardParams) == sizeof(HandRewardParams), "MiHandRewardParams layout");
-static_assert(sizeof(MiHandParams) == sizeof(HandParams), "MiHandParams layout");
-
 static thread_local std::string g_err;
 static int fail(const std::string& m) { g_err = m; return -1; }
+static int result(const std::string& err) { return err.empty() ? 0 : fail(err); }       // of a call into engine_core.hpp
 extern "C" const char* mi_last_error(void) { return g_err.c_str(); }
 extern "C" int mi_abi_version(void) { return MI_ABI_VERSION; }
 
-static bool cpu_task(int t) { return t >= 0 && t < kNumTasks; }      // every task of the table has a host build
-static void build_task_extras(int t, int n, Layout& L, MiEngine* e, char* base) {
-    if (is_hand_task(t)) build_hand_layout(t, n, L, e ? &e->hv : nullptr, base);
-    if (t == T_QUADCOPTER) build_quad_layout(n, L, e ? &e->qv : nullptr, base);
-    if (t == T_INGENUITY) build_ingenuity_layout(n, L, e ? &e->iv : nullptr, base);
-    if (t == T_BALLBALANCE) build_bbot_layout(n, L, e ? &e->bv : nullptr, base);
-}
-
-extern "C" int mi_task_info(const char* task, MiTaskInfo* out) {
-    const int t = task ? find_task(task) : -1;
-    if (t < 0 || !out) return fail(std::string("unknown task: ") + (task ? task : "(null)"));
-    const TaskMeta& m = kTasks[t];
-    out->num_obs = m.nobs; out->num_actions = m.nact; out->num_dofs = m.nd; out->num_bodies = m.nb; out->num_sensors = m.nsens;
-    out->num_contact_spheres = m.nsph; out->fixed_base = m.fixed; out->task_params_bytes = (int)m.pbytes;
-    return 0;
-}
-extern "C" size_t mi_engine_arena_bytes(const char* task, int num_envs) {
-    const int t = task ? find_task(task) : -1;
-    if (t < 0 || num_envs <= 0 || !cpu_task(t)) { fail("mi_engine_arena_bytes: task not available on the CPU backend"); return 0; }
-    Layout L;
-    build_layout(t, num_envs, L, nullptr, nullptr);      // (a narrower ShadowHand observationType only uses a prefix of obs_buf / obs_out)
-    build_task_extras(t, num_envs, L, nullptr, nullptr);
-    return L.off;
+extern "C" int mi_task_info(const char* task, MiTaskInfo* out) { return result(core_task_info(task, out)); }
+extern "C" size_t mi_engine_arena_bytes(const char* task, int num_envs) {      // every task of the table has a host build
+    const size_t n = core_arena_bytes(task, num_envs);
+    if (n == 0) fail("mi_engine_arena_bytes: bad task or num_envs");
+    return n;
 }
 extern "C" int mi_engine_create(const char* task, const MiSimParams* sim, const void* task_params, size_t task_params_bytes, int num_envs,
                                 int env_id_offset, uint64_t seed, void* arena, size_t arena_bytes, MiEngine** out) {
-    if (!task || !sim || !task_params || !arena || !out) return fail("mi_engine_create: null argument");
-    const int t = find_task(task);
-    if (t < 0) return fail(std::string("unknown task: ") + task);
-    if (task_params_bytes != kTasks[t].pbytes) return fail("mi_engine_create: task_params size mismatch");
-    if (num_envs <= 0) return fail("mi_engine_create: num_envs <= 0");
-    if (sim->substeps < 1 || sim->dt <= 0.f) return fail("mi_engine_create: invalid sim params");
+    EngineCore core;
+    if (int rc = result(core_create(core, task, sim, task_params, task_params_bytes, num_envs, env_id_offset, seed, arena, arena_bytes, out))) return rc;
     MiEngine* e = new (std::nothrow) MiEngine();
     if (!e) return fail("out of host memory");
-    e->task = t; e->N = num_envs; e->steps = 0; e->control_freq_inv = 1; e->clip_obs = INFINITY; e->num_threads = 4;   // cfg/config.yaml:30
-    memcpy(&e->P, sim, sizeof(SimParams));
-    if (t == T_CARTPOLE) memcpy(&e->cart, task_params, sizeof(CartpoleParams));
-    else if (t == T_QUADCOPTER) memcpy(&e->quad, task_params, sizeof(QuadcopterParams));
-    else if (t == T_INGENUITY) memcpy(&e->ing, task_params, sizeof(IngenuityParams));
-    else if (t == T_BALLBALANCE) memcpy(&e->bbot, task_params, sizeof(BallBalanceParams));
-    else if (t == T_ANYMAL) memcpy(&e->anymal, task_params, sizeof(AnymalParams));
-    else if (t == T_ANYMAL_FLAT) memcpy(&e->anymal_flat, task_params, sizeof(AnymalFlatParams));
-    else if (is_hand_task(t)) memcpy(&e->hand, task_params, sizeof(HandParams));
-    else if (t == T_ARTICULATION) {
-        memcpy(e->artic, task_params, sizeof(MiArticulationParams));
-        const MiScene& sc = ((const MiArticulationParams*)task_params)->scene;       // the check of mi_engine.hip
-        for (int i = 0; i < sc.n_free && i < MI_SCENE_MAX_FREE; ++i)
-            if (((sc.free_shape >> (4 * i)) & 15) > MI_SHAPE_CAPSULE) {
-                delete e;
-                return fail("mi_engine_create: MiScene.free_shape holds an unknown shape code (0 box, 1 sphere, 2 capsule)");
-            }
-    }
-    else memcpy(&e->loco, task_params, sizeof(LocoParams));
-    memset(&e->terrain, 0, sizeof(e->terrain));
-    e->terrain.walls = 1;
-    e->max_init_level = 0;
-    int nobs = 0;
-    if (is_hand_task(t)) {          // the checks of mi_engine.hip
-        const HandParams& hp = e->hand;
-        const int nfull = kTasks[t].nobs;     // ShadowHand 211, AllegroHand 88
-        const bool ok = (hp.obs_type == 0 && hp.num_obs == nfull) || (hp.obs_type >= 1 && hp.obs_type <= 3 && hp.num_obs >= 1 && hp.num_obs <= 160);
-        if (!ok) { delete e; return fail("mi_engine_create: hand task obs_type / num_obs invalid"); }
-        if (hp.object_shape < 0 || hp.object_shape > 2) { delete e; return fail("mi_engine_create: hand task object_shape must be 0 (block), 1 (pen) or 2 (egg)"); }
-        if (hp.object_shape != 0)
-            for (int k = 0; k < 3; ++k)
-                if ((!(hp.object_dims[k] > 0.f) && !(hp.object_shape == 1 && k == 2)) || !(hp.object_inertia[k] > 0.f)) {
-                    delete e;
-                    return fail("mi_engine_create: hand task egg / pen need positive object_dims / object_inertia");
-                }
-        if (!(hp.cube_mass > 0.f)) { delete e; return fail("mi_engine_create: hand task object mass must be positive"); }
-        for (int k = 0; hp.obs_type != 0 && k < hp.num_obs; ++k)
-            if (hp.obs_map[k] < 0 || hp.obs_map[k] >= nfull) { delete e; return fail("mi_engine_create: hand task obs_map entry out of range"); }
-        nobs = hp.num_obs;
-    }
-    if (t == T_INGENUITY && e->ing.target_period < 1) { delete e; return fail("mi_engine_create: Ingenuity target_period must be positive"); }
-    if (t == T_BALLBALANCE && !(e->bbot.ball_mass > 0.f && e->bbot.ball_inertia > 0.f && e->bbot.ball_radius > 0.f && e->bbot.pin_stiffness + e->bbot.pin_damping > 0.f)) {
-        delete e;
-        return fail("mi_engine_create: BallBalance needs positive ball mass / inertia / radius and a non-zero attractor");
-    }
-    memset(&e->v, 0, sizeof(View));
-    memset(&e->qv, 0, sizeof(e->qv)); memset(&e->iv, 0, sizeof(e->iv)); memset(&e->bv, 0, sizeof(e->bv)); memset(&e->hv, 0, sizeof(e->hv));
-    e->hv.drive_clamp = 1;
-    // the asset's hand-to-hand contact pairs (Shadow Hand, shared.xml:31-51) are on by default; the Allegro hand's URDF lists none
-    e->hv.pair_k = (t == T_SHADOWHAND) ? 2.0e4f : 0.f;
-    e->hv.tips_in_post = 1;
-    e->hv.pre_parts = 4;
-    Layout L;
-    build_layout(t, num_envs, L, &e->v, (char*)arena, nobs);
-    build_task_extras(t, num_envs, L, e, (char*)arena);
-    if (arena_bytes < L.off) { delete e; return fail("mi_engine_create: arena too small"); }
-    e->descs = L.d;
-    e->lamp_arena = e->v.lamp;
-    e->dof_api_arena = e->v.dof_api;
-    e->actor_scale_arena = e->v.actor_scale; e->limit_shift_arena = e->v.limit_shift;
-    e->v.actor_scale = nullptr; e->v.limit_shift = nullptr;
-    e->v.N = num_envs; e->v.env_offset = env_id_offset; e->v.seed = (uint32_t)(seed ^ (seed >> 32));
-    e->v.clip_obs = INFINITY;
+    static_cast<EngineCore&>(*e) = core;
+    e->num_threads = 4;   // cfg/config.yaml:30
     *out = e;
     return 0;
 }
 extern "C" void mi_engine_destroy(MiEngine* e) { delete e; }
 extern "C" int mi_engine_num_tensors(const MiEngine* e) { return e ? (int)e->descs.size() : fail("null engine"); }
-extern "C" int mi_engine_tensor_desc(const MiEngine* e, int i, MiTensorDesc* out) {
-    if (!e || !out || i < 0 || i >= (int)e->descs.size()) return fail("mi_engine_tensor_desc: bad index");
-    *out = e->descs[i];
-    return 0;
-}
-extern "C" int mi_engine_set_option(MiEngine* e, const char* key, double value) {
-    if (!e) return fail("null engine");
-    if (!strcmp(key, "clip_obs")) { e->clip_obs = (float)value; e->v.clip_obs = (float)value; return 0; }
-    if (!strcmp(key, "gravity_x")) { e->P.g[0] = (float)value; return 0; }
-    if (!strcmp(key, "gravity_y")) { e->P.g[1] = (float)value; return 0; }
-    if (!strcmp(key, "gravity_z")) { e->P.g[2] = (float)value; return 0; }
-    if (!strcmp(key, "control_freq_inv")) { if (value < 1) return fail("control_freq_inv < 1"); e->control_freq_inv = (int)value; return 0; }
-    if (!strcmp(key, "self_collision")) {
-        if (value != 0 && !e->lamp_arena) return fail("self_collision: this task's actor has no self-collision tables");
-        e->v.lamp = value != 0 ? e->lamp_arena : nullptr;
-        return 0;
-    }
-    if (!strcmp(key, "multi_wave") || !strcmp(key, "fused_sub") || !strcmp(key, "fused_post")) return 0;     // GPU launch shapes: nothing to do here
-    if (!strcmp(key, "dof_state_lag")) {        // AnymalTerrain: PD law / observations / reward read the dof state of the task's last refresh (1, default, the
-        // reference's behaviour: anymal_terrain.py:441-455 + vec_task.py:379-382) or the physics state (0).  Switching it on re-synchronises the tensor.
-        if (e->task != T_ANYMAL) return fail("dof_state_lag: an AnymalTerrain option");
-        if (value != 0 && e->v.dof_api == nullptr) memcpy(e->dof_api_arena, e->v.dof, (size_t)2 * kTasks[e->task].nd * e->N * sizeof(float));
-        e->v.dof_api = value != 0 ? e->dof_api_arena : nullptr; return 0;
-    }
-    if (!strcmp(key, "hand_body_mass")) {       // ShadowHand: the sub-step reads the per-body link-mass factors of `hand_body_mass_scale` (0, default: it does not)
-        if (e->task != T_SHADOWHAND) return fail("hand_body_mass: a ShadowHand option (the Allegro hand's kernels take one mass factor per env)");
-        e->hv.body_mass = value != 0 ? e->hv.body_mass_arena : nullptr; return 0;
-    }
-    if (!strcmp(key, "hand_pair_stiffness")) {  // hands: N/m of the compliant hand-to-hand contact pairs; 0 = the pairs off
-        if (!is_hand_task(e->task)) return fail("hand_pair_stiffness: a hand-task option");
-        if (!(value >= 0)) return fail("hand_pair_stiffness: >= 0");
-        e->hv.pair_k = (float)value; return 0;
-    }
-    if (!strcmp(key, "drive_force_limit")) {
-        if (!is_hand_task(e->task)) return fail("drive_force_limit: a hand-task option");
-        e->hv.drive_clamp = value != 0 ? 1 : 0; return 0;
-    }
-    if (!strcmp(key, "terrain_slope_threshold")) {   // terrain.slopeTreshold of the mesh generator (anymal_terrain.py:576); 0 = off
-        if (e->task != T_ANYMAL) return fail("terrain_slope_threshold: only AnymalTerrain has a terrain");
-        e->terrain.slope_threshold = (float)value;
-        return 0;
-    }
-    if (!strcmp(key, "terrain_walls")) {
-        if (e->task != T_ANYMAL) return fail("terrain_walls: only AnymalTerrain has a terrain");
-        e->terrain.walls = value != 0 ? 1 : 0;
-        return 0;
-    }
-    if (!strcmp(key, "actor_tensors")) {
-        if (is_hand_task(e->task)) return 0;         // the hands always read their own factor tensors
-        if (value != 0 && e->actor_scale_arena == nullptr) return fail("actor_tensors: this task carries no actor_scale / dof_limit_shift tensors");
-        e->v.actor_scale = value != 0 ? e->actor_scale_arena : nullptr;
-        e->v.limit_shift = value != 0 ? e->limit_shift_arena : nullptr;
-        return 0;
-    }
-    if (!strcmp(key, "steps")) { if (value < 0) return fail("steps < 0"); e->steps = (unsigned long long)value; return 0; }
+extern "C" int mi_engine_tensor_desc(const MiEngine* e, int i, MiTensorDesc* out) { return result(core_tensor_desc(e, i, out)); }
+
+// the options only this library has, or answers in its own way (the others: engine_core.hpp kCoreOptions)
+static const EngineOption kCpuOptions[] = {
+    // GPU launch shapes: accepted, nothing to do here
+    {"multi_wave", MI_ON_CPU, MI_SET { return {}; }, MI_GET { return 0; }},
+    {"fused_sub", MI_ON_CPU, MI_SET { return {}; }, MI_GET { return 0; }},
+    {"fused_post", MI_ON_CPU, MI_SET { return {}; }, MI_GET { return 0; }},
+    {"dof_state_lag", MI_ON_CPU, MI_SET {
+         return core_set_dof_state_lag(e, x, [&](size_t bytes) -> std::string { memcpy(e.dof_api_arena, e.v.dof, bytes); return {}; }); },
+     core_get_dof_state_lag},
     // sim.physx.num_threads of the reference's CPU pipeline (vec_task.py:541, cfg/config.yaml:30): OpenMP threads over envs
-    if (!strcmp(key, "num_threads")) { if (value < 1) return fail("num_threads < 1"); e->num_threads = (int)value; return 0; }
-    return fail(std::string("unknown option: ") + key);
-}
-static_assert(sizeof(MiNoiseParams) == sizeof(NoiseParams), "MiNoiseParams layout");
-extern "C" int mi_engine_set_noise(MiEngine* e, int which, const MiNoiseParams* p) {
-    if (!e || !p) return fail("mi_engine_set_noise: null argument");
-    if (which != 0 && which != 1) return fail("mi_engine_set_noise: which must be 0 (observations) or 1 (actions)");
-    if (p->dist < 0 || p->dist > 2 || p->op < 0 || p->op > 1) return fail("mi_engine_set_noise: dist in {0,1,2}, op in {0,1}");
-    if (e->task != T_CARTPOLE && e->task != T_ANT && e->task != T_HUMANOID && !is_hand_task(e->task) && p->dist != 0)
-        return fail("mi_engine_set_noise: in-kernel noise exists for Cartpole, Ant, Humanoid and ShadowHand");
-    memcpy(which == 0 ? &e->v.obs_noise : &e->v.act_noise, p, sizeof(NoiseParams));
-    return 0;
-}
-extern "C" int mi_engine_get_option(const MiEngine* e, const char* key, double* out) {
-    if (!e || !key || !out) return fail("mi_engine_get_option: null argument");
-    if (!strcmp(key, "clip_obs")) { *out = e->clip_obs; return 0; }
-    if (!strcmp(key, "gravity_x")) { *out = e->P.g[0]; return 0; }
-    if (!strcmp(key, "gravity_y")) { *out = e->P.g[1]; return 0; }
-    if (!strcmp(key, "gravity_z")) { *out = e->P.g[2]; return 0; }
-    if (!strcmp(key, "control_freq_inv")) { *out = e->control_freq_inv; return 0; }
-    if (!strcmp(key, "self_collision")) { *out = e->v.lamp != nullptr ? 1.0 : 0.0; return 0; }
-    if (!strcmp(key, "multi_wave") || !strcmp(key, "fused_sub") || !strcmp(key, "fused_post")) { *out = 0; return 0; }
-    if (!strcmp(key, "drive_force_limit")) { *out = is_hand_task(e->task) ? e->hv.drive_clamp : 0; return 0; }
-    if (!strcmp(key, "dof_state_lag")) { *out = (e->task == T_ANYMAL && e->v.dof_api != nullptr) ? 1 : 0; return 0; }
-    if (!strcmp(key, "hand_body_mass")) { *out = (is_hand_task(e->task) && e->hv.body_mass != nullptr) ? 1 : 0; return 0; }
-    if (!strcmp(key, "hand_pair_stiffness")) { *out = is_hand_task(e->task) ? e->hv.pair_k : 0; return 0; }
-    if (!strcmp(key, "terrain_slope_threshold")) { *out = e->terrain.slope_threshold; return 0; }
-    if (!strcmp(key, "terrain_walls")) { *out = e->terrain.walls; return 0; }
-    if (!strcmp(key, "actor_tensors")) { *out = (is_hand_task(e->task) || e->v.actor_scale != nullptr) ? 1.0 : 0.0; return 0; }
-    if (!strcmp(key, "steps")) { *out = (double)e->steps; return 0; }
-    if (!strcmp(key, "num_threads")) { *out = e->num_threads; return 0; }
-    return fail(std::string("unknown option: ") + key);
-}
-extern "C" int mi_engine_last_ring(const MiEngine* e) { return e ? (int)((e->steps + 1) & 1) : -1; }
+    {"num_threads", MI_ON_CPU, MI_SET { if (x < 1) return "num_threads < 1"; static_cast<MiEngine&>(e).num_threads = (int)x; return {}; },
+     MI_GET { return static_cast<const MiEngine&>(e).num_threads; }},
+};
+extern "C" int mi_engine_set_option(MiEngine* e, const char* key, double value) { return result(core_set_option(e, key, value, MI_ON_CPU, kCpuOptions)); }
+extern "C" int mi_engine_get_option(const MiEngine* e, const char* key, double* out) { return result(core_get_option(e, key, out, MI_ON_CPU, kCpuOptions)); }
+extern "C" int mi_engine_set_noise(MiEngine* e, int which, const MiNoiseParams* p) { return result(core_set_noise(e, which, p)); }
+extern "C" int mi_engine_last_ring(const MiEngine* e) { return core_last_ring(e); }
 // the terrain arrays are copied: the engine does not depend on the caller keeping its buffers alive
 extern "C" int mi_engine_set_terrain(MiEngine* e, const int16_t* height_samples, int rows, int cols, float horizontal_scale, float vertical_scale,
                                      float border_size, const float* env_origins, int num_levels, int num_terrains, float env_length, int max_init_level) {
-    if (!e) return fail("null engine");
-    if (e->task != T_ANYMAL) return fail("mi_engine_set_terrain: only AnymalTerrain uses a terrain");
-    if (!height_samples || !env_origins || rows < 2 || cols < 2 || num_levels < 1 || num_terrains < 1 || horizontal_scale <= 0.f)
-        return fail("mi_engine_set_terrain: bad argument");
+    if (int rc = result(core_check_terrain_args(e, height_samples, rows, cols, horizontal_scale, env_origins, num_levels, num_terrains))) return rc;
     e->terrain_hs.assign(height_samples, height_samples + (size_t)rows * cols);
     e->terrain_origins.assign(env_origins, env_origins + (size_t)num_levels * num_terrains * 3);
-    e->terrain.hs = e->terrain_hs.data(); e->terrain.rows = rows; e->terrain.cols = cols;
-    e->terrain.hscale = horizontal_scale; e->terrain.vscale = vertical_scale; e->terrain.border = border_size;
-    e->terrain.origins = e->terrain_origins.data(); e->terrain.levels = num_levels; e->terrain.types = num_terrains;
-    e->terrain.env_length = env_length;
-    e->max_init_level = max_init_level < 0 ? 0 : (max_init_level >= num_levels ? num_levels - 1 : max_init_level);
+    core_set_terrain(*e, e->terrain_hs.data(), rows, cols, horizontal_scale, vertical_scale, border_size, e->terrain_origins.data(), num_levels, num_terrains,
+                     env_length, max_init_level);
     return 0;
 }
 static int hand_call(MiEngine* e, int what, const float* actions, bool simulate_only, const int64_t* ids, int n, float* out_j, float* out_h) {
@@ -256,45 +86,18 @@ static int hand_call(MiEngine* e, int what, const float* actions, bool simulate_
 extern "C" int mi_engine_init_state(MiEngine* e, void*) {
     if (!e) return fail("null engine");
     const TaskMeta& m = kTasks[e->task];
-    const View& v = e->v;
-    const int N = v.N, nd = m.nd;
+    const int N = e->N;
     if (is_hand_task(e->task)) {
         e->steps = 0;
         const int rc = hand_call(e, 0, nullptr, false, nullptr, 0, nullptr, nullptr);
         return rc == -2 ? fail("mi_engine_init_state: the hand model of this library and its task table have different sizes (a variant built without its engine unit)") : rc;
     }
     if (e->task == T_ANYMAL && e->terrain.hs == nullptr) return fail("mi_engine_init_state: AnymalTerrain needs mi_engine_set_terrain first");
-    const bool loco = e->task == T_ANT || e->task == T_HUMANOID;
-    const float root_z = e->task == T_CARTPOLE ? 2.0f : e->task == T_QUADCOPTER ? e->quad.init_height : e->task == T_INGENUITY ? e->ing.init_height
-                       : e->task == T_BALLBALANCE ? e->bbot.tray_height : e->task == T_ANYMAL ? e->anymal.base_init_state[2]
-                       : e->task == T_ANYMAL_FLAT ? e->anymal_flat.base_init_state[2]
-                       : e->task == T_ARTICULATION ? reinterpret_cast<const MiArticulationParams*>(e->artic)->init_root[2] : e->loco.start_height;      // cartpole.py:93 / ant.py:164 / the tasks' default poses
-    const float pot0 = loco ? -1000.f / e->loco.dt : 0.f;                                   // ant.py:113
+    const float root_z = core_init_root_z(*e);
     const float root[13] = {0, 0, root_z, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0};
-    for (int en = 0; en < N; ++en) {
-        for (int k = 0; k < 13; ++k) { v.root[k * N + en] = root[k]; v.init_root[k * N + en] = root[k]; }
-        for (int k = 0; k < nd; ++k) {
-            v.dof[k * N + en] = loco ? e->loco.initial_dof_pos[k] : 0.f;
-            v.dof[(nd + k) * N + en] = 0.f;
-            v.tau[k * N + en] = 0.f; v.laml[k * N + en] = 0.f; v.dof_force[k * N + en] = 0.f;
-        }
-        for (int k = 0; k < 3 * m.nsph; ++k) v.lamc[k * N + en] = 0.f;
-        if (v.lamp) for (int k = 0; k < 3 * ModelHumanoid::NPG; ++k) { v.lamp[k * N + en] = 0.f; v.pairf[k * N + en] = 0.f; }
-        if (v.dropped) { v.dropped[en] = 0; v.dropped[N + en] = 0; }
-        for (int k = 0; k < 6 * m.nsens; ++k) v.sensor[k * N + en] = 0.f;
-        for (int k = 0; k < m.nact; ++k) v.actions[k * N + en] = 0.f;
-        for (int k = 0; k < m.nobs; ++k) { v.obs[(size_t)en * m.nobs + k] = 0.f; v.obs_out[(size_t)en * m.nobs + k] = 0.f; v.obs_out[((size_t)N + en) * m.nobs + k] = 0.f; }
-        v.potentials[en] = pot0; v.prev_potentials[en] = pot0;
-        if (v.friction) v.friction[en] = -1.f;
-        if (e->actor_scale_arena) for (int k = 0; k < v.nas; ++k) e->actor_scale_arena[k * N + en] = 1.f;
-        if (e->limit_shift_arena) for (int k = 0; k < 2 * nd; ++k) e->limit_shift_arena[k * N + en] = 0.f;
-        for (int k = 0; k < 3; ++k) { v.up_vec[k * N + en] = (k == 2) ? 1.f : 0.f; v.heading_vec[k * N + en] = (k == 0) ? 1.f : 0.f; }
-        v.rew[en] = 0.f;
-        v.reset[en] = 1;      // vec_task.py:316-317: every env is reset inside the first step()
-        v.progress[en] = 0; v.randomize[en] = 0; v.timeout[en] = 0; v.episode[en] = 0;
-        v.ep_ret[en] = 0.f;
-    }
-    for (int k = 0; k < 8; ++k) v.stats[k] = 0.f;
+    const View v0 = init_view(*e);
+    for (int en = 0; en < N; ++en)
+        init_env_constants(v0, en, m.nd, 3 * m.nsph, 6 * m.nsens, m.nobs, m.nact, root_z, core_is_loco(*e) ? e->loco.initial_dof_pos : nullptr, core_init_potential(*e));
     for (int en = 0; en < N; ++en) {      // the tasks' own tensors (quad_init_kernel / ing_init_kernel / bbot_init_kernel)
         if (e->task == T_QUADCOPTER) {
             for (int d = 0; d < kQuadDof; ++d) e->qv.targets[d * N + en] = 0.f;

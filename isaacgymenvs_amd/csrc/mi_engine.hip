@@ -10,8 +10,7 @@
 
 #include "../../include/mi_engine.h"
 #include "step_kernels.hpp"
-#include "arena_layout.hpp"
-#include "task_views.hpp"
+#include "engine_core.hpp"
 #include "gen/model_ant.h"
 #include "gen/model_cartpole.h"
 #include "gen/model_humanoid.h"
@@ -21,26 +20,12 @@
 #include "tasks/anymal.hpp"
 #include "gen/model_quadcopter.h"
 #include "tasks/quadcopter.hpp"
-#include "tasks/shadow_hand.hpp"
-#include "tasks/articulation.hpp"
 
 using namespace mi;
 
-static_assert(sizeof(MiSimParams) == sizeof(SimParams), "MiSimParams layout");
-static_assert(sizeof(MiLocoParams) == sizeof(LocoParams), "MiLocoParams layout");
-static_assert(sizeof(MiCartpoleParams) == sizeof(CartpoleParams), "MiCartpoleParams layout");
-static_assert(MI_MAX_DOF == mi::kMaxDof, "MI_MAX_DOF");
-static_assert(sizeof(MiAnymalParams) == sizeof(AnymalParams), "MiAnymalParams layout");
-static_assert(sizeof(MiAnymalFlatParams) == sizeof(AnymalFlatParams), "MiAnymalFlatParams layout");
-static_assert(sizeof(MiQuadcopterParams) == sizeof(QuadcopterParams), "MiQuadcopterParams layout");
-static_assert(sizeof(MiIngenuityParams) == sizeof(IngenuityParams), "MiIngenuityParams layout");
-static_assert(sizeof(MiBallBalanceParams) == sizeof(BallBalanceParams), "MiBallBalanceParams layout");
-static_assert(sizeof(MiHandRewardParams) == sizeof(HandRewardParams), "MiHandRewardParams layout");
-static_assert(sizeof(MiHandParams) == sizeof(HandParams), "MiHandParams layout");
-static_assert(sizeof(MiArticulationParams) == sizeof(ArticulationParams), "MiArticulationParams layout");
-
 static thread_local std::string g_err;
 static int fail(const std::string& m) { g_err = m; return -1; }
+static int result(const std::string& err) { return err.empty() ? 0 : fail(err); }       // of a call into engine_core.hpp
 namespace mi { int abi_fail(const char* msg) { return fail(msg); } }   // for the entry points that live in other translation units
 extern "C" const char* mi_last_error(void) { return g_err.c_str(); }
 extern "C" int mi_abi_version(void) { return MI_ABI_VERSION; }
@@ -51,31 +36,8 @@ extern "C" int mi_abi_version(void) { return MI_ABI_VERSION; }
 __global__ void init_state_kernel(View v, int nd, int nsph3, int nsens6, int nobs, int nact, float root_z,
                                   const float* __restrict__ init_dof /* [nd] or null */, float pot0) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = v.N;
-    if (e >= N) return;
-    const float root[13] = {0, 0, root_z, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < 13; ++k) { v.root[k * N + e] = root[k]; v.init_root[k * N + e] = root[k]; }
-    for (int k = 0; k < nd; ++k) {
-        v.dof[k * N + e] = init_dof ? init_dof[k] : 0.f;
-        v.dof[(nd + k) * N + e] = 0.f;
-        v.tau[k * N + e] = 0.f; v.laml[k * N + e] = 0.f; v.dof_force[k * N + e] = 0.f;
-    }
-    for (int k = 0; k < nsph3; ++k) v.lamc[k * N + e] = 0.f;
-    if (v.lamp) for (int k = 0; k < 3 * ModelHumanoid::NPG; ++k) { v.lamp[k * N + e] = 0.f; v.pairf[k * N + e] = 0.f; }
-    if (v.dropped) { v.dropped[e] = 0; v.dropped[N + e] = 0; }
-    for (int k = 0; k < nsens6; ++k) v.sensor[k * N + e] = 0.f;
-    for (int k = 0; k < nact; ++k) v.actions[k * N + e] = 0.f;
-    for (int k = 0; k < nobs; ++k) { v.obs[(size_t)e * nobs + k] = 0.f; v.obs_out[(size_t)e * nobs + k] = 0.f; v.obs_out[((size_t)N + e) * nobs + k] = 0.f; }
-    v.potentials[e] = pot0; v.prev_potentials[e] = pot0;
-    if (v.friction) v.friction[e] = -1.f;       // model friction until somebody writes the tensor (AnymalTerrain's init overwrites it)
-    if (v.actor_scale) for (int k = 0; k < v.nas; ++k) v.actor_scale[k * N + e] = 1.f;
-    if (v.limit_shift) for (int k = 0; k < 2 * nd; ++k) v.limit_shift[k * N + e] = 0.f;
-    for (int k = 0; k < 3; ++k) { v.up_vec[k * N + e] = (k == 2) ? 1.f : 0.f; v.heading_vec[k * N + e] = (k == 0) ? 1.f : 0.f; }
-    v.rew[e] = 0.f;
-    v.reset[e] = 1;  // vec_task.py:316-317: every env is reset inside the first step()
-    v.progress[e] = 0; v.randomize[e] = 0; v.timeout[e] = 0; v.episode[e] = 0;
-    v.ep_ret[e] = 0.f;
-    if (e == 0) for (int k = 0; k < 8; ++k) v.stats[k] = 0.f;
+    if (e >= v.N) return;
+    init_env_constants(v, e, nd, nsph3, nsens6, nobs, nact, root_z, init_dof, pot0);
 }
 
 // ------------------------------------------------------------------------------------------------ stand-alone jit-fn replacements
@@ -199,7 +161,7 @@ hipError_t launch_simulate_anymal(const View& v, const SimParams& P, const Anyma
 hipError_t launch_init_anymal(const View& v, const AnymalParams& tp, const AnymalTerrainDesc& T, int max_init_level, hipStream_t s);
 hipError_t launch_reset_anymal(const View& v, const AnymalParams& tp, const AnymalTerrainDesc& T, const long long* ids, int n, hipStream_t s);
 }
-namespace mi {  // defined in kernels_shadow_hand.hip
+namespace mi {  // defined in kernels_anymal.hip, kernels_quadcopter.hip, kernels_ingenuity.hip, kernels_ball_balance.hip
 hipError_t launch_step_anymal_flat(const View& v, const SimParams& P, const AnymalFlatParams& tp, const float* actions, int cfi, hipStream_t s);
 hipError_t launch_simulate_anymal_flat(const View& v, const SimParams& P, const AnymalFlatParams& tp, hipStream_t s);
 hipError_t launch_init_anymal_flat(const View& v, const AnymalFlatParams& tp, hipStream_t s);
@@ -244,278 +206,61 @@ hipError_t launch_simulate_allegro_hand(const View& v, const HandView& hv, const
 hipError_t launch_init_allegro_hand(const View& v, const HandView& hv, const HandParams& p, hipStream_t s);
 hipError_t launch_reset_allegro_hand(const View& v, const HandView& hv, const HandParams& p, const long long* ids, int n, hipStream_t s);
 }
-struct MiEngine {
-    int task, N;
-    SimParams P;
-    LocoParams loco;
-    CartpoleParams cart;
-    AnymalParams anymal;
-    AnymalFlatParams anymal_flat;
-    QuadcopterParams quad;
-    QuadView qv;
-    IngenuityParams ing;
-    IngenuityView iv;
-    BallBalanceParams bbot;
-    BbotView bv;
-    AnymalTerrainDesc terrain;
-    HandParams hand;
-    HandView hv;
-    ArticulationParams artic;
-    int max_init_level;
+struct MiEngine : EngineCore {
     int device;            // HIP device the caller's arena lives on: every entry point must be called with it current
-    View v;
-    float clip_obs;
-    int control_freq_inv;
-    std::vector<MiTensorDesc> descs;
-    unsigned long long steps;
-    // the `actor_params` tensors (actor_scale, dof_limit_shift) of Ant / Humanoid: the kernels only read them once the option
-    // "actor_tensors" is on -- with the option off (default) the sub-step runs on the model's constants and skips the loads
-    float* actor_scale_arena;
-    float* limit_shift_arena;
-    float* lamp_arena;     // the self-contact impulse tensor (Humanoid), kept while the option self_collision is 0
-    float* dof_api_arena;  // the refreshed dof-state tensor (AnymalTerrain), kept while the option dof_state_lag is 0
 };
 
-extern "C" int mi_task_info(const char* task, MiTaskInfo* out) {
-    int t = find_task(task);
-    if (t < 0) return fail(std::string("unknown task: ") + task);
-    const TaskMeta& m = kTasks[t];
-    out->num_obs = m.nobs; out->num_actions = m.nact; out->num_dofs = m.nd; out->num_bodies = m.nb;
-    out->num_sensors = m.nsens; out->num_contact_spheres = m.nsph; out->fixed_base = m.fixed;
-    out->task_params_bytes = (int)m.pbytes;
-    return 0;
-}
-
+extern "C" int mi_task_info(const char* task, MiTaskInfo* out) { return result(core_task_info(task, out)); }
 extern "C" size_t mi_engine_arena_bytes(const char* task, int num_envs) {
-    int t = find_task(task);
-    if (t < 0 || num_envs <= 0) { fail("mi_engine_arena_bytes: bad task or num_envs"); return 0; }
-    Layout L;
-    build_layout(t, num_envs, L, nullptr, nullptr);
-    if (is_hand_task(t)) build_hand_layout(t, num_envs, L, nullptr, nullptr);
-    if (t == T_QUADCOPTER) build_quad_layout(num_envs, L, nullptr, nullptr);
-    if (t == T_INGENUITY) build_ingenuity_layout(num_envs, L, nullptr, nullptr);
-    if (t == T_BALLBALANCE) build_bbot_layout(num_envs, L, nullptr, nullptr);
-    return L.off;
+    const size_t n = core_arena_bytes(task, num_envs);
+    if (n == 0) fail("mi_engine_arena_bytes: bad task or num_envs");
+    return n;
 }
 
 extern "C" int mi_engine_create(const char* task, const MiSimParams* sim, const void* task_params, size_t task_params_bytes,
                                 int num_envs, int env_id_offset, uint64_t seed, void* arena, size_t arena_bytes,
                                 MiEngine** out) {
-    int t = find_task(task);
-    if (t < 0) return fail(std::string("unknown task: ") + task);
-    if (!sim || !task_params || !arena || !out) return fail("mi_engine_create: null argument");
-    if (num_envs <= 0) return fail("mi_engine_create: num_envs must be positive");
-    if (task_params_bytes != kTasks[t].pbytes) return fail("mi_engine_create: task_params size mismatch (ABI)");
-    if (sim->substeps < 1 || sim->dt <= 0.f) return fail("mi_engine_create: invalid sim params");
+    EngineCore core;
+    if (int rc = result(core_create(core, task, sim, task_params, task_params_bytes, num_envs, env_id_offset, seed, arena, arena_bytes, out))) return rc;
     MiEngine* e = new (std::nothrow) MiEngine();
     if (!e) return fail("out of host memory");
-    e->task = t; e->N = num_envs; e->steps = 0; e->control_freq_inv = 1; e->clip_obs = INFINITY;
-    memcpy(&e->P, sim, sizeof(SimParams));
-    memset(&e->terrain, 0, sizeof(e->terrain));
-    e->terrain.walls = 1;
-    e->max_init_level = 0;
-    if (t == T_CARTPOLE) memcpy(&e->cart, task_params, sizeof(CartpoleParams));
-    else if (t == T_ANYMAL) memcpy(&e->anymal, task_params, sizeof(AnymalParams));
-    else if (t == T_ANYMAL_FLAT) memcpy(&e->anymal_flat, task_params, sizeof(AnymalFlatParams));
-    else if (t == T_QUADCOPTER) memcpy(&e->quad, task_params, sizeof(QuadcopterParams));
-    else if (t == T_INGENUITY) {
-        memcpy(&e->ing, task_params, sizeof(IngenuityParams));
-        if (e->ing.target_period < 1) { delete e; return fail("mi_engine_create: Ingenuity target_period must be positive"); }
-    }
-    else if (t == T_BALLBALANCE) {
-        memcpy(&e->bbot, task_params, sizeof(BallBalanceParams));
-        const BallBalanceParams& b = e->bbot;
-        if (!(b.ball_mass > 0.f) || !(b.ball_inertia > 0.f) || !(b.ball_radius > 0.f) || !(b.pin_stiffness >= 0.f) || !(b.pin_damping >= 0.f) ||
-            !(b.pin_stiffness + b.pin_damping > 0.f)) {
-            delete e;
-            return fail("mi_engine_create: BallBalance needs positive ball mass / inertia / radius and a non-zero attractor");
-        }
-    }
-    else if (is_hand_task(t)) memcpy(&e->hand, task_params, sizeof(HandParams));
-    else if (t == T_ARTICULATION) {
-        memcpy(&e->artic, task_params, sizeof(ArticulationParams));
-        if (!scene_shapes_known(e->artic.scene.n_free, e->artic.scene.free_shape)) {
-            delete e;
-            return fail("mi_engine_create: MiScene.free_shape holds an unknown shape code (0 box, 1 sphere, 2 capsule)");
-        }
-    }
-    else memcpy(&e->loco, task_params, sizeof(LocoParams));
-    Layout L;
-    memset(&e->v, 0, sizeof(View));
-    e->v.fused_post = 0;
-    e->v.fused_sub = 0;
-    int nobs = 0;
-    if (is_hand_task(t)) {
-        const HandParams& hp = e->hand;
-        const int nfull = kTasks[t].nobs;     // ShadowHand 211, AllegroHand 88
-        const bool ok = (hp.obs_type == 0 && hp.num_obs == nfull) || (hp.obs_type >= 1 && hp.obs_type <= 3 && hp.num_obs >= 1 && hp.num_obs <= 160);
-        if (!ok) { delete e; return fail("mi_engine_create: hand task obs_type / num_obs invalid"); }
-        if (hp.object_shape < 0 || hp.object_shape > 2) { delete e; return fail("mi_engine_create: hand task object_shape must be 0 (block), 1 (pen) or 2 (egg)"); }
-        if (hp.object_shape != 0)
-            for (int k = 0; k < 3; ++k)
-                if ((!(hp.object_dims[k] > 0.f) && !(hp.object_shape == 1 && k == 2)) || !(hp.object_inertia[k] > 0.f)) {
-                    delete e;
-                    return fail("mi_engine_create: hand task egg / pen need positive object_dims / object_inertia");
-                }
-        if (!(hp.cube_mass > 0.f)) { delete e; return fail("mi_engine_create: hand task object mass must be positive"); }
-        for (int k = 0; hp.obs_type != 0 && k < hp.num_obs; ++k)
-            if (hp.obs_map[k] < 0 || hp.obs_map[k] >= nfull) { delete e; return fail("mi_engine_create: hand task obs_map entry out of range"); }
-        nobs = hp.num_obs;
-    }
-    build_layout(t, num_envs, L, &e->v, (char*)arena, nobs);
-    e->lamp_arena = e->v.lamp;       // self-collision is on by default where the reference's actor collides with itself
-    e->dof_api_arena = e->v.dof_api; // (AnymalTerrain: the task's lagging dof-state tensor is on by default, as in the reference)
-    e->actor_scale_arena = e->v.actor_scale; e->limit_shift_arena = e->v.limit_shift;
-    e->v.actor_scale = nullptr; e->v.limit_shift = nullptr;
-    memset(&e->hv, 0, sizeof(e->hv));
-    e->hv.drive_clamp = 1;
-    // the asset's hand-to-hand contact pairs (Shadow Hand, shared.xml:31-51) are on by default; the Allegro hand's URDF lists none
-    e->hv.pair_k = (t == T_SHADOWHAND) ? 2.0e4f : 0.f;
-    e->hv.tips_in_post = 1;
-    e->hv.pre_parts = 4;
-    if (is_hand_task(t)) build_hand_layout(t, num_envs, L, &e->hv, (char*)arena);
-    memset(&e->qv, 0, sizeof(e->qv));
-    if (t == T_QUADCOPTER) build_quad_layout(num_envs, L, &e->qv, (char*)arena);
-    memset(&e->iv, 0, sizeof(e->iv));
-    if (t == T_INGENUITY) build_ingenuity_layout(num_envs, L, &e->iv, (char*)arena);
-    memset(&e->bv, 0, sizeof(e->bv));
-    if (t == T_BALLBALANCE) build_bbot_layout(num_envs, L, &e->bv, (char*)arena);
-    if (arena_bytes < L.off) { delete e; return fail("mi_engine_create: arena too small"); }
-    e->descs = L.d;
-    {
-        // a host arena is accepted for layout inspection (mi_engine_tensor_desc); every launching entry point refuses it
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, arena) == hipSuccess && attr.type == hipMemoryTypeDevice) e->device = attr.device;
-        else { (void)hipGetLastError(); e->device = -1; }
-    }
-    e->v.N = num_envs; e->v.env_offset = env_id_offset; e->v.seed = (uint32_t)(seed ^ (seed >> 32));
-    e->v.clip_obs = INFINITY;
+    static_cast<EngineCore&>(*e) = core;
+    // a host arena is accepted for layout inspection (mi_engine_tensor_desc); every launching entry point refuses it
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, arena) == hipSuccess && attr.type == hipMemoryTypeDevice) e->device = attr.device;
+    else { (void)hipGetLastError(); e->device = -1; }
     *out = e;
     return 0;
 }
 
 extern "C" void mi_engine_destroy(MiEngine* e) { delete e; }
 extern "C" int mi_engine_num_tensors(const MiEngine* e) { return e ? (int)e->descs.size() : fail("null engine"); }
-extern "C" int mi_engine_tensor_desc(const MiEngine* e, int i, MiTensorDesc* out) {
-    if (!e || !out || i < 0 || i >= (int)e->descs.size()) return fail("mi_engine_tensor_desc: bad index");
-    *out = e->descs[i];
-    return 0;
-}
-// optional knobs (env.clipObservations vec_task.py:115, env.controlFrequencyInv :111)
-extern "C" int mi_engine_set_option(MiEngine* e, const char* key, double value) {
-    if (!e) return fail("null engine");
-    if (!strcmp(key, "clip_obs")) { e->clip_obs = (float)value; e->v.clip_obs = (float)value; return 0; }
-    // sim_params.gravity randomisation (reference vec_task.py:720-732 -> gym.set_sim_params)
-    if (!strcmp(key, "gravity_x")) { e->P.g[0] = (float)value; return 0; }
-    if (!strcmp(key, "gravity_y")) { e->P.g[1] = (float)value; return 0; }
-    if (!strcmp(key, "gravity_z")) { e->P.g[2] = (float)value; return 0; }
-    if (!strcmp(key, "control_freq_inv")) { if (value < 1) return fail("control_freq_inv < 1"); e->control_freq_inv = (int)value; return 0; }
-    // self-collision of the actor (reference: the collision filter passed to gym.create_actor, humanoid.py:194 uses 0 = collide);
-    // only tasks whose arena has the self_contact_impulse tensor accept 1
-    if (!strcmp(key, "self_collision")) {
-        if (value != 0 && !e->lamp_arena) return fail("self_collision: this task's actor has no self-collision tables");
-        e->v.lamp = value != 0 ? e->lamp_arena : nullptr;
-        return 0;
-    }
+extern "C" int mi_engine_tensor_desc(const MiEngine* e, int i, MiTensorDesc* out) { return result(core_tensor_desc(e, i, out)); }
+
+// the options only this library has, or answers in its own way (the others: engine_core.hpp kCoreOptions)
+static const EngineOption kHipOptions[] = {
     // multi-wave sub-step (core/engine_mw.hpp, core/engine_mwc.hpp): envs per workgroup, 0 = one wave per workgroup.  Ignored by tasks
     // whose model has no multi-wave form (Cartpole, Quadcopter).  ShadowHand: any non-zero value selects the finger-per-wave form (32 envs per
     // workgroup, core/hand_engine_mw.hpp).  2: the Humanoid's round-2 form (main wave + self-collision helper).
-    if (!strcmp(key, "multi_wave")) {
-        const bool hand64 = value == 64 && is_hand_task(e->task);        // full 64-env waves, one workgroup per CU (hand_mw_kernels.hpp)
-        // 8: the Ant's one-launch kernel (sub-steps + post step) on 8-env workgroups, two per CU (mw_kernels.hpp); every other launch of such an engine
-        // takes the 32-env shape
-        const bool ant8 = MI_MW_HAS8 && value == 8 && e->task == T_ANT;       // (an A/B build only: -DMI_MW_HAS8=1)
-        if (value != 0 && value != 32 && value != 2 && !(MI_MW_HAS16 && value == 16) && !hand64 && !ant8) return fail("multi_wave: 0, 16 or 32 (envs per workgroup); 2: main + helper wave; 8: Ant only; 64: ShadowHand / AllegroHand only");
-        e->v.mw = (int)value;
-        return 0;
-    }
-    // limb-per-wave locomotion (Ant): 1 = post_physics_step runs on one wave of every sub-step workgroup at the end of the step's last
-    // sub-step launch (mw_kernels.hpp), 0 (default) = in loco_post_kernel as for the one-wave form
-    if (!strcmp(key, "pre_parts")) {           // hands: lanes per env of the pre kernel, 4 (default) or 1
-        if (!is_hand_task(e->task)) return fail("pre_parts: a hand-task option");
-        if (value != 1 && value != 4) return fail("pre_parts: 1 or 4");
-        e->hv.pre_parts = (int)value; return 0;
-    }
-    if (!strcmp(key, "tips_in_post")) {        // hands: fingertip states by the post kernel's fingertip groups (1, default) or by hand_tips_kernel (0)
-        if (!is_hand_task(e->task)) return fail("tips_in_post: a hand-task option");
-        e->hv.tips_in_post = value != 0 ? 1 : 0; return 0;
-    }
-    if (!strcmp(key, "dof_state_lag")) {        // AnymalTerrain: PD law / observations / reward read the dof state of the task's last refresh (1, default, the
-        // reference's behaviour: anymal_terrain.py:441-455 + vec_task.py:379-382) or the physics state (0).  Switching it on re-synchronises the tensor.
-        if (e->task != T_ANYMAL) return fail("dof_state_lag: an AnymalTerrain option");
-        if (value != 0 && e->v.dof_api == nullptr)      // back on: the tensor starts from the physics state (a synchronous copy: this is a set-up call)
-            HIP_OK(hipMemcpy(e->dof_api_arena, e->v.dof, (size_t)2 * kTasks[e->task].nd * e->N * sizeof(float), hipMemcpyDeviceToDevice));
-        e->v.dof_api = value != 0 ? e->dof_api_arena : nullptr; return 0;
-    }
-    if (!strcmp(key, "hand_body_mass")) {       // ShadowHand: the sub-step reads the per-body link-mass factors of `hand_body_mass_scale` (0, default: it does not)
-        if (e->task != T_SHADOWHAND) return fail("hand_body_mass: a ShadowHand option (the Allegro hand's kernels take one mass factor per env)");
-        e->hv.body_mass = value != 0 ? e->hv.body_mass_arena : nullptr; return 0;
-    }
-    if (!strcmp(key, "hand_pair_stiffness")) {  // hands: N/m of the compliant hand-to-hand contact pairs; 0 = the pairs off
-        if (!is_hand_task(e->task)) return fail("hand_pair_stiffness: a hand-task option");
-        if (!(value >= 0)) return fail("hand_pair_stiffness: >= 0");
-        e->hv.pair_k = (float)value; return 0;
-    }
-    if (!strcmp(key, "drive_force_limit")) {   // hands: the position drives deliver at most their force range (shared.xml:250-269, allegro_hand.py:264); default 1
-        if (!is_hand_task(e->task)) return fail("drive_force_limit: a hand-task option");
-        e->hv.drive_clamp = value != 0 ? 1 : 0; return 0;
-    }
-    if (!strcmp(key, "fused_post")) { e->v.fused_post = value != 0 ? 1 : 0; return 0; }
-    if (!strcmp(key, "fused_sub")) { e->v.fused_sub = value != 0 ? 1 : 0; return 0; }
-    // control-step counter (observation ring parity, AnymalTerrain push schedule, noise counters): part of a state checkpoint
-    if (!strcmp(key, "steps")) { if (value < 0) return fail("steps < 0"); e->steps = (unsigned long long)value; return 0; }
-    if (!strcmp(key, "actor_tensors")) {   // 1: the sub-step reads actor_scale / dof_limit_shift (Ant, Humanoid); ShadowHand always reads its own
-        if (is_hand_task(e->task)) return 0;
-        if (value != 0 && e->actor_scale_arena == nullptr) return fail("actor_tensors: this task carries no actor_scale / dof_limit_shift tensors");
-        e->v.actor_scale = value != 0 ? e->actor_scale_arena : nullptr;
-        e->v.limit_shift = value != 0 ? e->limit_shift_arena : nullptr;
-        return 0;
-    }
-    if (!strcmp(key, "terrain_slope_threshold")) {   // terrain.slopeTreshold of the mesh generator (anymal_terrain.py:576); 0 = off
-        if (e->task != T_ANYMAL) return fail("terrain_slope_threshold: only AnymalTerrain has a terrain");
-        e->terrain.slope_threshold = (float)value;
-        return 0;
-    }
-    if (!strcmp(key, "terrain_walls")) {   // the vertical faces of the slope-corrected triangle mesh (anymal_terrain.py:198-211, :576) collide from the side
-        if (e->task != T_ANYMAL) return fail("terrain_walls: only AnymalTerrain has a terrain");
-        e->terrain.walls = value != 0 ? 1 : 0;
-        return 0;
-    }
-    return fail(std::string("unknown option: ") + key);
-}
-static_assert(sizeof(MiNoiseParams) == sizeof(NoiseParams), "MiNoiseParams layout");
-extern "C" int mi_engine_set_noise(MiEngine* e, int which, const MiNoiseParams* p) {
-    if (!e || !p) return fail("mi_engine_set_noise: null argument");
-    if (which != 0 && which != 1) return fail("mi_engine_set_noise: which must be 0 (observations) or 1 (actions)");
-    if (p->dist < 0 || p->dist > 2 || p->op < 0 || p->op > 1) return fail("mi_engine_set_noise: dist in {0,1,2}, op in {0,1}");
-    if (e->task != T_CARTPOLE && e->task != T_ANT && e->task != T_HUMANOID && !is_hand_task(e->task) && p->dist != 0)
-        return fail("mi_engine_set_noise: in-kernel noise exists for Cartpole, Ant, Humanoid and ShadowHand");
-    memcpy(which == 0 ? &e->v.obs_noise : &e->v.act_noise, p, sizeof(NoiseParams));
-    return 0;
-}
-extern "C" int mi_engine_get_option(const MiEngine* e, const char* key, double* out) {
-    if (!e || !key || !out) return fail("mi_engine_get_option: null argument");
-    if (!strcmp(key, "clip_obs")) { *out = e->clip_obs; return 0; }
-    if (!strcmp(key, "gravity_x")) { *out = e->P.g[0]; return 0; }
-    if (!strcmp(key, "gravity_y")) { *out = e->P.g[1]; return 0; }
-    if (!strcmp(key, "gravity_z")) { *out = e->P.g[2]; return 0; }
-    if (!strcmp(key, "control_freq_inv")) { *out = e->control_freq_inv; return 0; }
-    if (!strcmp(key, "self_collision")) { *out = e->v.lamp != nullptr ? 1.0 : 0.0; return 0; }
-    if (!strcmp(key, "multi_wave")) { *out = e->v.mw; return 0; }
-    if (!strcmp(key, "drive_force_limit")) { *out = is_hand_task(e->task) ? e->hv.drive_clamp : 0; return 0; }
-    if (!strcmp(key, "dof_state_lag")) { *out = (e->task == T_ANYMAL && e->v.dof_api != nullptr) ? 1 : 0; return 0; }
-    if (!strcmp(key, "hand_body_mass")) { *out = (is_hand_task(e->task) && e->hv.body_mass != nullptr) ? 1 : 0; return 0; }
-    if (!strcmp(key, "hand_pair_stiffness")) { *out = is_hand_task(e->task) ? e->hv.pair_k : 0; return 0; }
-    if (!strcmp(key, "tips_in_post")) { *out = is_hand_task(e->task) ? e->hv.tips_in_post : 0; return 0; }
-    if (!strcmp(key, "pre_parts")) { *out = is_hand_task(e->task) ? e->hv.pre_parts : 0; return 0; }
-    if (!strcmp(key, "fused_post")) { *out = e->v.fused_post; return 0; }
-    if (!strcmp(key, "fused_sub")) { *out = e->v.fused_sub; return 0; }
-    if (!strcmp(key, "steps")) { *out = (double)e->steps; return 0; }
-    if (!strcmp(key, "terrain_slope_threshold")) { *out = e->terrain.slope_threshold; return 0; }
-    if (!strcmp(key, "terrain_walls")) { *out = e->terrain.walls; return 0; }
-    if (!strcmp(key, "actor_tensors")) { *out = (is_hand_task(e->task) || e->v.actor_scale != nullptr) ? 1.0 : 0.0; return 0; }
-    return fail(std::string("unknown option: ") + key);
-}
+    {"multi_wave", MI_ON_HIP, MI_SET {
+         const bool hand64 = x == 64 && is_hand_task(e.task);        // full 64-env waves, one workgroup per CU (hand_mw_kernels.hpp)
+         // 8: the Ant's one-launch kernel (sub-steps + post step) on 8-env workgroups, two per CU (mw_kernels.hpp); every other launch of such an engine
+         // takes the 32-env shape
+         const bool ant8 = MI_MW_HAS8 && x == 8 && e.task == T_ANT;       // (an A/B build only: -DMI_MW_HAS8=1)
+         if (x != 0 && x != 32 && x != 2 && !(MI_MW_HAS16 && x == 16) && !hand64 && !ant8)
+             return "multi_wave: 0, 16 or 32 (envs per workgroup); 2: main + helper wave; 8: Ant only; 64: ShadowHand / AllegroHand only";
+         e.v.mw = (int)x; return {}; },
+     MI_GET { return e.v.mw; }},
+    {"dof_state_lag", MI_ON_HIP, MI_SET {
+         return core_set_dof_state_lag(e, x, [&](size_t bytes) -> std::string {
+             const hipError_t rc = hipMemcpy(e.dof_api_arena, e.v.dof, bytes, hipMemcpyDeviceToDevice);
+             return rc == hipSuccess ? std::string() : std::string("dof_state_lag: hipMemcpy: ") + hipGetErrorString(rc);
+         }); },
+     core_get_dof_state_lag},
+};
+extern "C" int mi_engine_set_option(MiEngine* e, const char* key, double value) { return result(core_set_option(e, key, value, MI_ON_HIP, kHipOptions)); }
+extern "C" int mi_engine_get_option(const MiEngine* e, const char* key, double* out) { return result(core_get_option(e, key, out, MI_ON_HIP, kHipOptions)); }
+extern "C" int mi_engine_set_noise(MiEngine* e, int which, const MiNoiseParams* p) { return result(core_set_noise(e, which, p)); }
 
 // kernels launch on the current device; the arena belongs to one device
 static int check_device(const MiEngine* e, const char* where) {
@@ -528,101 +273,47 @@ static int check_device(const MiEngine* e, const char* where) {
     return 0;
 }
 
-// the view the initial-state kernel writes through: the `actor_params` tensors are initialised whether the kernels read them or not
-static View init_view(const MiEngine* e) {
-    View v = e->v;
-    v.actor_scale = e->actor_scale_arena; v.limit_shift = e->limit_shift_arena;
-    return v;
-}
 extern "C" int mi_engine_init_state(MiEngine* e, void* stream) {
     if (!e) return fail("null engine");
     if (int rc = check_device(e, "mi_engine_init_state")) return rc;
     hipStream_t s = (hipStream_t)stream;
     const TaskMeta& m = kTasks[e->task];
-    float* d_init = nullptr;
-    float root_z = 0.f, pot0 = 0.f;
-    if (is_hand_task(e->task)) {
+    if (is_hand_task(e->task)) {      // an initial state of their own
         if (e->task == T_SHADOWHAND) HIP_OK(launch_init_shadow_hand(e->v, e->hv, e->hand, s));
         else HIP_OK(launch_init_allegro_hand(e->v, e->hv, e->hand, s));
         e->steps = 0;
         return 0;
     }
-    if (e->task == T_QUADCOPTER) {
-        const int blocks = (e->N + 255) / 256;
-        hipLaunchKernelGGL(init_state_kernel, dim3(blocks), dim3(256), 0, s, init_view(e), m.nd, 3 * m.nsph, 6 * m.nsens, m.nobs, m.nact,
-                           e->quad.init_height, (const float*)nullptr, 0.f);
-        HIP_OK(hipGetLastError());
-        HIP_OK(launch_init_quadcopter(e->v, e->qv, e->quad, s));
-        e->steps = 0;
-        return 0;
-    }
-    if (e->task == T_INGENUITY) {
-        const int blocks = (e->N + 255) / 256;
-        hipLaunchKernelGGL(init_state_kernel, dim3(blocks), dim3(256), 0, s, init_view(e), m.nd, 3 * m.nsph, 6 * m.nsens, m.nobs, m.nact,
-                           e->ing.init_height, (const float*)nullptr, 0.f);
-        HIP_OK(hipGetLastError());
-        HIP_OK(launch_init_ingenuity(e->v, e->iv, e->ing, s));
-        e->steps = 0;
-        return 0;
-    }
-    if (e->task == T_BALLBALANCE) {
-        const int blocks = (e->N + 255) / 256;
-        hipLaunchKernelGGL(init_state_kernel, dim3(blocks), dim3(256), 0, s, init_view(e), m.nd, 3 * m.nsph, 6 * m.nsens, m.nobs, m.nact,
-                           e->bbot.tray_height, (const float*)nullptr, 0.f);
-        HIP_OK(hipGetLastError());
-        HIP_OK(launch_init_ball_balance(e->v, e->bv, e->bbot, s));
-        e->steps = 0;
-        return 0;
-    }
-    if (e->task == T_ARTICULATION) {
-        const int blocks = (e->N + 255) / 256;
-        hipLaunchKernelGGL(init_state_kernel, dim3(blocks), dim3(256), 0, s, init_view(e), m.nd, 3 * m.nsph, 6 * m.nsens, m.nobs, m.nact,
-                           e->artic.init_root[2], (const float*)nullptr, 0.f);
-        HIP_OK(hipGetLastError());
-        HIP_OK(launch_reset_articulation(e->v, e->artic, nullptr, e->N, s));
-        e->steps = 0;
-        return 0;
-    }
-    if (e->task == T_ANYMAL_FLAT) {
-        const int blocks = (e->N + 255) / 256;
-        hipLaunchKernelGGL(init_state_kernel, dim3(blocks), dim3(256), 0, s, init_view(e), m.nd, 3 * m.nsph, 0, m.nobs, m.nact,
-                           e->anymal_flat.base_init_state[2], (const float*)nullptr, 0.f);
-        HIP_OK(hipGetLastError());
-        HIP_OK(launch_init_anymal_flat(e->v, e->anymal_flat, s));
-        e->steps = 0;
-        return 0;
-    }
-    if (e->task == T_ANYMAL) {
-        if (e->terrain.hs == nullptr) return fail("mi_engine_init_state: AnymalTerrain needs mi_engine_set_terrain first");
-        const int blocks = (e->N + 255) / 256;
-        hipLaunchKernelGGL(init_state_kernel, dim3(blocks), dim3(256), 0, s, init_view(e), m.nd, 3 * m.nsph, 0, m.nobs, m.nact,
-                           e->anymal.base_init_state[2], (const float*)nullptr, 0.f);
-        HIP_OK(hipGetLastError());
-        HIP_OK(launch_init_anymal(e->v, e->anymal, e->terrain, e->max_init_level, s));
-        // the constructor's reset_idx(arange(num_envs)) (anymal_terrain.py:170)
-        long long* ids = nullptr;
-        HIP_OK(hipMalloc(&ids, sizeof(long long) * e->N));
-        std::vector<long long> h(e->N);
-        for (int i = 0; i < e->N; ++i) h[i] = i;
-        HIP_OK(hipMemcpyAsync(ids, h.data(), sizeof(long long) * e->N, hipMemcpyHostToDevice, s));
-        HIP_OK(launch_reset_anymal(e->v, e->anymal, e->terrain, ids, e->N, s));
-        HIP_OK(hipStreamSynchronize(s));
-        HIP_OK(hipFree(ids));
-        e->steps = 0;
-        return 0;
-    }
-    if (e->task != T_CARTPOLE) {
+    if (e->task == T_ANYMAL && e->terrain.hs == nullptr) return fail("mi_engine_init_state: AnymalTerrain needs mi_engine_set_terrain first");
+    float* d_init = nullptr;        // Ant / Humanoid: the start joint positions, on the device for the kernel
+    if (core_is_loco(*e)) {
         HIP_OK(hipMalloc(&d_init, sizeof(float) * m.nd));
         HIP_OK(hipMemcpyAsync(d_init, e->loco.initial_dof_pos, sizeof(float) * m.nd, hipMemcpyHostToDevice, s));
-        root_z = e->loco.start_height;
-        pot0 = -1000.f / e->loco.dt;  // ant.py:113
-    } else {
-        root_z = 2.0f;  // cartpole.py:93
     }
-    const int blocks = (e->N + 255) / 256;
-    hipLaunchKernelGGL(init_state_kernel, dim3(blocks), dim3(256), 0, s, init_view(e), m.nd, 3 * m.nsph, 6 * m.nsens, m.nobs, m.nact,
-                       root_z, d_init, pot0);
+    hipLaunchKernelGGL(init_state_kernel, dim3((e->N + 255) / 256), dim3(256), 0, s, init_view(*e), m.nd, 3 * m.nsph, 6 * m.nsens, m.nobs, m.nact,
+                       core_init_root_z(*e), (const float*)d_init, core_init_potential(*e));
     HIP_OK(hipGetLastError());
+    switch (e->task) {          // the task's own tensors and its constructor's reset
+        case T_QUADCOPTER: HIP_OK(launch_init_quadcopter(e->v, e->qv, e->quad, s)); break;
+        case T_INGENUITY: HIP_OK(launch_init_ingenuity(e->v, e->iv, e->ing, s)); break;
+        case T_BALLBALANCE: HIP_OK(launch_init_ball_balance(e->v, e->bv, e->bbot, s)); break;
+        case T_ARTICULATION: HIP_OK(launch_reset_articulation(e->v, e->artic, nullptr, e->N, s)); break;
+        case T_ANYMAL_FLAT: HIP_OK(launch_init_anymal_flat(e->v, e->anymal_flat, s)); break;
+        case T_ANYMAL: {
+            HIP_OK(launch_init_anymal(e->v, e->anymal, e->terrain, e->max_init_level, s));
+            // the constructor's reset_idx(arange(num_envs)) (anymal_terrain.py:170)
+            long long* ids = nullptr;
+            HIP_OK(hipMalloc(&ids, sizeof(long long) * e->N));
+            std::vector<long long> h(e->N);
+            for (int i = 0; i < e->N; ++i) h[i] = i;
+            HIP_OK(hipMemcpyAsync(ids, h.data(), sizeof(long long) * e->N, hipMemcpyHostToDevice, s));
+            HIP_OK(launch_reset_anymal(e->v, e->anymal, e->terrain, ids, e->N, s));
+            HIP_OK(hipStreamSynchronize(s));
+            HIP_OK(hipFree(ids));
+            break;
+        }
+        default: break;
+    }
     if (d_init) { HIP_OK(hipStreamSynchronize(s)); HIP_OK(hipFree(d_init)); }
     e->steps = 0;
     return 0;
@@ -659,7 +350,7 @@ extern "C" int mi_engine_step(MiEngine* e, const float* actions, void* stream) {
     e->steps++;
     return 0;
 }
-extern "C" int mi_engine_last_ring(const MiEngine* e) { return e ? (int)((e->steps + 1) & 1) : -1; }
+extern "C" int mi_engine_last_ring(const MiEngine* e) { return core_last_ring(e); }
 
 extern "C" int mi_engine_simulate(MiEngine* e, void* stream) {
     if (!e) return fail("null engine");
@@ -733,18 +424,13 @@ extern "C" int mi_engine_reset_idx(MiEngine* e, const int64_t* env_ids, int n, v
     return 0;
 }
 
+// the engine reads the caller's device arrays: they stay alive as long as the engine does
 extern "C" int mi_engine_set_terrain(MiEngine* e, const int16_t* height_samples, int rows, int cols, float horizontal_scale,
                                      float vertical_scale, float border_size, const float* env_origins, int num_levels,
                                      int num_terrains, float env_length, int max_init_level) {
-    if (!e) return fail("null engine");
-    if (e->task != T_ANYMAL) return fail("mi_engine_set_terrain: only AnymalTerrain uses a terrain");
-    if (!height_samples || !env_origins || rows < 2 || cols < 2 || num_levels < 1 || num_terrains < 1 || horizontal_scale <= 0.f)
-        return fail("mi_engine_set_terrain: bad argument");
-    e->terrain.hs = (const short*)height_samples; e->terrain.rows = rows; e->terrain.cols = cols;
-    e->terrain.hscale = horizontal_scale; e->terrain.vscale = vertical_scale; e->terrain.border = border_size;
-    e->terrain.origins = env_origins; e->terrain.levels = num_levels; e->terrain.types = num_terrains;
-    e->terrain.env_length = env_length;
-    e->max_init_level = max_init_level < 0 ? 0 : (max_init_level >= num_levels ? num_levels - 1 : max_init_level);
+    if (int rc = result(core_check_terrain_args(e, height_samples, rows, cols, horizontal_scale, env_origins, num_levels, num_terrains))) return rc;
+    core_set_terrain(*e, (const short*)height_samples, rows, cols, horizontal_scale, vertical_scale, border_size, env_origins, num_levels, num_terrains,
+                     env_length, max_init_level);
     return 0;
 }
 

@@ -134,6 +134,7 @@ typedef struct {
  * unpinned against the closed simulator). */
 #define MI_SCENE_MAX_FREE 4
 #define MI_SCENE_MAX_STATIC 4
+#define MI_SCENE_MAX_STATIC_WIDE 12 /* static boxes of a library whose Articulation unit was built wide (mi_engine_set_scene_statics below) */
 #define MI_SHAPE_BOX 0
 #define MI_SHAPE_SPHERE 1
 #define MI_SHAPE_CAPSULE 2
@@ -304,6 +305,17 @@ int mi_engine_compute_mass_matrices(MiEngine* e, float* out, void* stream);
 int mi_engine_set_terrain(MiEngine* e, const int16_t* height_samples, int rows, int cols, float horizontal_scale,
                           float vertical_scale, float border_size, const float* env_origins, int num_levels,
                           int num_terrains, float env_length, int max_init_level);
+/* Fixed-base Articulation scenes: replaces the engine's WHOLE set of static boxes by n boxes -- pos [n][3], quat [n][4] xyzw, half [n][3] half
+ * sizes, mu [n] shape frictions, HOST arrays that are copied.  Host only, like mi_engine_set_terrain: the next mi_engine_simulate uses the new set.
+ * Never called: the set is MiScene.static_* (at most MI_SCENE_MAX_STATIC boxes).  n may reach the library's static capacity (option
+ * "scene_static_capacity"): MI_SCENE_MAX_STATIC for the stock library and every variant built as before, MI_SCENE_MAX_STATIC_WIDE for a variant
+ * whose Articulation unit was compiled with -DMI_SCENE_STATIC_CAP=12 (a ring wall of eight boxes around a plate) -- that library's scene sub-step
+ * is the wide form of csrc/core/scene_engine.hpp (64-bit broad-phase mask, 12 statics in its work area).  MiScene, MiArticulationParams and the arena
+ * are the same for both; an additive export, the ABI version stays.  After this call MiScene.static_* / n_static inside the engine mirror only the
+ * FIRST MI_SCENE_MAX_STATIC boxes of the set: on a wide library n_static no longer tells how many statics are simulated (the set's n does), and
+ * n = 0 on an engine without free bodies leaves no scene at all -- the actor alone on the ground plane.  Non-zero with mi_last_error for: n < 0, n above the capacity, a null array with
+ * n > 0, a non-positive half size, a quaternion whose norm is off 1 by more than 1e-3, an engine that is not a fixed-base Articulation scene. */
+int mi_engine_set_scene_statics(MiEngine* e, int n, const float* pos, const float* quat, const float* half, const float* mu);
 /* optional knobs: "clip_obs" (env.clipObservations, vec_task.py:115), "control_freq_inv" (env.controlFrequencyInv, :111),
  * "gravity_x|y|z" (gym.set_sim_params after sim_params.gravity randomisation, vec_task.py:720-732),
  * "self_collision" 0 | 1 (the collision filter of gym.create_actor: humanoid.py:194 passes 0 = the actor collides with itself;
@@ -339,7 +351,8 @@ typedef struct MiNoiseParams {
     uint32_t epoch;        /* stream id of the correlated draws (0: sampled once, as the reference does) */
 } MiNoiseParams;
 int mi_engine_set_noise(MiEngine* e, int which, const MiNoiseParams* params);
-/* reads back any of the keys of mi_engine_set_option (replaces gym.get_sim_params / gym.get_frame_count, vec_task.py:620,723) */
+/* reads back any of the keys of mi_engine_set_option (replaces gym.get_sim_params / gym.get_frame_count, vec_task.py:620,723); read-only keys:
+ * "scene_static_capacity" (Articulation: static boxes the library's scene holds, MI_SCENE_MAX_STATIC or MI_SCENE_MAX_STATIC_WIDE; 0 for other tasks) */
 int mi_engine_get_option(const MiEngine* e, const char* key, double* value);
 /* which slot of the "obs_out" ring ([2, N, num_obs], clamped copy of obs_buf = what VecTask.step returns as
  * obs_dict["obs"], vec_task.py:402) the most recent step wrote */

@@ -170,16 +170,25 @@ def dependent_sources(model_name):
     return out
 
 
-def variant_library(model_name, spec, device="cuda", verbose=False, sensors=None):
-    """-> path of the library to create the engine from (the stock library when the header is the compiled model's own)"""
+def variant_library(model_name, spec, device="cuda", verbose=False, sensors=None, static_capacity=None):
+    """-> path of the library to create the engine from (the stock library when the header is the compiled model's own)
+    static_capacity: static boxes the Articulation robot's scene form holds -- None / 4: as ever (the same library, byte for byte); 12: the wide form
+    (csrc/core/scene_engine.hpp SceneSim<M, 12>), the build define MI_SCENE_STATIC_CAP of the robot's translation units, a cached library of its own"""
     from .. import native
+    cap = int(static_capacity or native.MI_SCENE_MAX_STATIC)
+    if cap not in (native.MI_SCENE_MAX_STATIC, native.MI_SCENE_MAX_STATIC_WIDE):
+        raise ValueError(f"static_capacity: {native.MI_SCENE_MAX_STATIC} or {native.MI_SCENE_MAX_STATIC_WIDE}")
     txt = header_text(model_name, spec, sensors)
     csrc = os.path.join(_PKG, "csrc")
     stock = open(os.path.join(csrc, "gen", f"model_{model_name}.h")).read()
     cpu = str(device).startswith("cpu")
-    if txt == stock:
+    wide = cap != native.MI_SCENE_MAX_STATIC
+    if wide and model_name != GENERIC_MODEL:
+        raise NotImplementedError("the wide static capacity is a build of the Articulation task's robot")
+    if txt == stock and not wide:
         return None
-    h = hashlib.sha1((txt + model_name).encode()).hexdigest()[:16]
+    # (the capacity joins the hashed text only when it is not the default: an unchanged variant keeps its directory and its library)
+    h = hashlib.sha1((txt + model_name + (f"|MI_SCENE_STATIC_CAP={cap}" if wide else "")).encode()).hexdigest()[:16]
     vdir = os.path.join(VARIANT_DIR, h)
     out = os.path.join(vdir, "libmi_engine_cpu.so" if cpu else "libmi_engine.so")
     stock_lib = native.CPU_LIB_PATH if cpu else native.LIB_PATH
@@ -193,14 +202,14 @@ def variant_library(model_name, spec, device="cuda", verbose=False, sensors=None
         try:
             if os.path.exists(out) and os.path.getmtime(out) >= os.path.getmtime(stock_lib):
                 return out
-            _build_variant(model_name, txt, vdir, out, cpu, verbose)
+            _build_variant(model_name, txt, vdir, out, cpu, verbose, [f"-DMI_SCENE_STATIC_CAP={cap}"] if wide else [])
             spec.save(os.path.join(vdir, "model.json"))
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
     return out
 
 
-def _build_variant(model_name, txt, vdir, out, cpu, verbose):
+def _build_variant(model_name, txt, vdir, out, cpu, verbose, extra_defs=()):
     from .. import native
     csrc = os.path.join(_PKG, "csrc")
     src = os.path.join(vdir, "csrc")
@@ -227,7 +236,7 @@ def _build_variant(model_name, txt, vdir, out, cpu, verbose):
         for s, suffix, opt, defs, models in native.CPU_UNITS:
             if models is None or model_name in models or (resized and s == "mi_engine_cpu.cpp"):
                 o = os.path.join(deep, "build", os.path.basename(native.cpu_object(s, suffix)))
-                cmd = ["g++", opt] + native.CPU_FLAGS + defs + ["-c", os.path.join(deep, "cpu", s), "-o", o]
+                cmd = ["g++", opt] + native.CPU_FLAGS + defs + list(extra_defs) + ["-c", os.path.join(deep, "cpu", s), "-o", o]
                 if verbose:
                     print(" ".join(cmd), flush=True)
                 procs.append((s, subprocess.Popen(cmd, cwd=deep, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
@@ -247,7 +256,7 @@ def _build_variant(model_name, txt, vdir, out, cpu, verbose):
         for s in native.SOURCES:
             if s in deps:
                 o = os.path.join(deep, "build", s.replace(".hip", ".o"))
-                cmd = [native.hipcc_path()] + native.HIPCC_FLAGS + ["-c", os.path.join(deep, s), "-o", o]
+                cmd = [native.hipcc_path()] + native.HIPCC_FLAGS + list(extra_defs) + ["-c", os.path.join(deep, s), "-o", o]
                 if verbose:
                     print(" ".join(cmd), flush=True)
                 procs.append((s, subprocess.Popen(cmd, cwd=deep, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

@@ -31,7 +31,7 @@ constexpr int kNumTasks = 11;
 // The Articulation task's robot is compiled at run time (assets/runtime.py): its constants live in ONE translation unit of each library
 // (kernels_articulation.hip / cpu/cpu_articulation.cpp), which is all a run-time variant has to recompile; everybody else learns the robot's sizes
 // from this function instead of including gen/model_articulation.h.
-struct ArticulationMeta { int nd, nb, nsens, nsph, fixed; };
+struct ArticulationMeta { int nd, nb, nsens, nsph, fixed, static_cap; };     // static_cap: static boxes the unit's scene form holds (4 or 12)
 ArticulationMeta mi_articulation_meta();
 static inline bool is_hand_task(int t) { return t == T_SHADOWHAND || t == T_ALLEGROHAND; }
 struct TaskMeta { const char* name; int nobs, nact, nd, nb, nsens, nsph, fixed; size_t pbytes; };

@@ -7,6 +7,7 @@
 // core/hand_engine.hpp is; what is specific here:
 //   * up to kSceneMaxFree free boxes (three half sizes, principal inertias along the box axes, gravity on) and kSceneMaxStatic static boxes
 //     (pose + half sizes), both RUN-TIME parameters (SceneParams = MiScene of include/mi_engine.h): one compiled robot serves any scene;
+//     the WIDE form SceneSim<M, kSceneMaxStaticWide> holds 12 static boxes (a SceneStatics block beside SceneParams, a 64-bit pair mask);
 //   * the actor's own gravity follows asset option disable_gravity (franka_cube_stack.py:199), the boxes' follows the sim;
 //   * contacts, every one 3 rows (normal + friction disc) of ONE Gauss-Seidel sequence with the actor's joint-limit rows:
 //       actor sphere (the model's collision spheres, meshes sampled by assets/mesh.py) vs free box / static box   [actor chain | 6 box dofs]
@@ -53,6 +54,7 @@
 namespace mi {
 
 constexpr int kSceneMaxFree = 4, kSceneMaxStatic = 4;
+constexpr int kSceneMaxStaticWide = 12;         // the WIDE form's static capacity (SceneSim<M, 12>): a ring wall of eight boxes, a plate, a bin
 struct SceneParams {        // mirrors MiScene (include/mi_engine.h)
     int n_free, n_static;
     int arm_gravity;        // 0: asset option disable_gravity on the articulated actor
@@ -61,6 +63,13 @@ struct SceneParams {        // mirrors MiScene (include/mi_engine.h)
     float free_init[kSceneMaxFree][7];      // start pose (create_actor): what reset leaves
     float static_pos[kSceneMaxStatic][3], static_quat[kSceneMaxStatic][4], static_half[kSceneMaxStatic][3], static_mu[kSceneMaxStatic];
     float arm_mu;           // friction of the actor's shapes (combined with the other side's by averaging, PhysX's default combine mode)
+};
+
+// The static boxes of the WIDE form (SceneSim<M, kSceneMaxStaticWide>; include/mi_engine.h mi_engine_set_scene_statics): a block of its own beside
+// SceneParams, whose layout (MiScene) holds four.  The sub-step copies it into the row store's work area with compile-time indices.
+struct SceneStatics {
+    int n;
+    float pos[kSceneMaxStaticWide][3], quat[kSceneMaxStaticWide][4], half[kSceneMaxStaticWide][3], mu[kSceneMaxStaticWide];
 };
 
 // point / sphere (centre c in the box frame, radius r) vs box of half sizes a[3]: signed distance, outward normal (box frame)
@@ -235,9 +244,13 @@ MI_HD void scene_face_crossings(const float* Rr, const float* xr, const float* h
     }
 }
 
-template <class M>
+// NSTAT: the static capacity, kSceneMaxStatic (the statics are SceneParams::static_*) or kSceneMaxStaticWide (they are a SceneStatics block; the
+// broad-phase mask of the box pairs is 64 bits, the work area holds NSTAT rotations / centres / half sizes and the statics' frictions)
+template <class M, int NSTAT = kSceneMaxStatic>
 struct SceneSim : Sim<M> {
     using B = Sim<M>;
+    static_assert(NSTAT == kSceneMaxStatic || NSTAT == kSceneMaxStaticWide, "SceneSim: static capacity 4 or 12");
+    static constexpr bool WIDE = NSTAT > kSceneMaxStatic;
     static constexpr int NB = M::NB, ND = M::ND, NV = M::NV, OFF = M::OFF, NSPH = M::NSPH, NSENS = M::NSENS, NLIM = B::NLIM, NVA = B::NVA;
     static_assert(M::FIXED == 1, "SceneSim: a fixed-base actor (the scene's free bodies are boxes, spheres and capsules)");
     static constexpr int KARM = 24, KBOX = 24;              // contact slots: actor spheres, box corners
@@ -251,8 +264,9 @@ struct SceneSim : Sim<M> {
     // ... | feature id (int bits, > 0)
     static constexpr int S_GEO = 3 * HCH, S_AUX = S_GEO + 6, S_CSZ = S_AUX + 11;
     static constexpr int KSLOT = KARM + KBOX;              // entries of the warm-start tensor: (feature, lam_n, lam_t1, lam_t2) per slot
-    static constexpr int NTGT = kSceneMaxFree + kSceneMaxStatic;
-    static_assert(kSceneMaxFree * NTGT <= 32, "the box pairs' broad-phase mask is one word");
+    static constexpr int NTGT = kSceneMaxFree + NSTAT;
+    using PMask = std::conditional_t<(kSceneMaxFree * NTGT <= 32), unsigned, unsigned long long>;
+    static_assert(kSceneMaxFree * NTGT <= 8 * (int)sizeof(PMask), "the box pairs' broad-phase mask is one word (capacity 4) or two (capacity 12: exactly 64 bits)");
     static_assert(KSLOT == 48, "tensor scene_warm holds MI_SCENE_WARM_SLOTS = 48 entries per env (include/mi_engine.h; checked against it in tasks/articulation.hpp)");
     static constexpr int R_LIMG = B::limoff(NLIM);
     static constexpr int R_CB = R_LIMG + 3 * NLIM;          // limit G | Ainv, vt, lam | contact slots
@@ -268,8 +282,9 @@ struct SceneSim : Sim<M> {
     // previous row wrote it: with the boxes in scratch each of those ~10^4 read-after-write pairs per sub-step was a round trip to memory (1.7 ms
     // per sub-step at ANY batch size; profiles/r5t_scene_time.txt)
     static constexpr int W_VB = R_BODY + NB, W_XF = W_VB + 6 * kSceneMaxFree, W_IINV = W_XF + 3 * kSceneMaxFree, W_IM = W_IINV + 9 * kSceneMaxFree,
-                         W_RF = W_IM + kSceneMaxFree, W_RS = W_RF + 9 * kSceneMaxFree, W_XST = W_RS + 9 * kSceneMaxStatic,
-                         W_HF = W_XST + 3 * kSceneMaxStatic, W_HS = W_HF + 3 * kSceneMaxFree, W_XS = W_HS + 3 * kSceneMaxStatic;
+                         W_RF = W_IM + kSceneMaxFree, W_RS = W_RF + 9 * kSceneMaxFree, W_XST = W_RS + 9 * NSTAT,
+                         W_HF = W_XST + 3 * NSTAT, W_HS = W_HF + 3 * kSceneMaxFree, W_MUS = W_HS + 3 * NSTAT,
+                         W_XS = W_MUS + (WIDE ? NSTAT : 0);      // (the statics' frictions: the wide form only -- capacity 4 reads them from SceneParams)
     static constexpr int ROW_SLOTS = W_XS + 3 * M::NSPHA;
 
     float box[kSceneMaxFree][13];                           // free boxes: pos3, quat xyzw, linvel3, angvel3 (world)
@@ -283,12 +298,13 @@ struct SceneSim : Sim<M> {
     // one sub-step of length h.  tau[ND]: efforts; drv: per-dof position drives; laml: warm-start limit impulses; ncontact: contacts taken
     // (actor + box) | refused for want of a slot << 16
     // warm: [4 * KSLOT] last sub-step's (feature, impulses) per slot, rewritten at the end (p == nullptr: no warm start)
+    // SX: the static boxes of the wide form (ignored by capacity 4, whose statics are SP.static_*)
     // vmax: [ND] the asset's joint velocity limits (<= 0: none): the solved joint velocities are clamped to them (the simulator enforces
     // maxJointVelocity; without it an arm under random operational-space commands reaches 70 rad/s and its task's matrix inverses blow up)
     template <int RS>
     MI_HD void substep_scene(const SimParams& P, const SceneParams& SP, const float* tau, const Drive& drv, const float h, const RowStore<RS> rows,
                              const Strided laml, const Strided dof_force, int* ncontact, const Strided warm = Strided{nullptr, 1},
-                             const float* vmax = nullptr, const Strided netf = Strided{nullptr, 1}) {
+                             const float* vmax = nullptr, const Strided netf = Strided{nullptr, 1}, const SceneStatics* SX = nullptr) {
         constexpr int ST = RowStore<RS>::stride;
         float (&q)[M::NDA] = this->q;
         float (&qd)[M::NDA] = this->qd;
@@ -298,7 +314,7 @@ struct SceneSim : Sim<M> {
         auto vt = [&](int row) MI_LAMBDA -> float& { return rows(R_LIMG + NLIM + row); };
         auto lam = [&](int row) MI_LAMBDA -> float& { return rows(R_LIMG + 2 * NLIM + row); };
         const float invh = MI_RCP(h);
-        const int nf = SP.n_free < kSceneMaxFree ? SP.n_free : kSceneMaxFree, ns = SP.n_static < kSceneMaxStatic ? SP.n_static : kSceneMaxStatic;
+        const int nf = SP.n_free < kSceneMaxFree ? SP.n_free : kSceneMaxFree, ns = WIDE ? (SX->n < NSTAT ? SX->n : NSTAT) : (SP.n_static < NSTAT ? SP.n_static : NSTAT);
         // shape of free body i: a scalar read of the kernel argument shifted by the body number (no run-time index into the struct, no LDS)
         auto shape_of = [&](int i) MI_LAMBDA -> int { return (SP.free_shape >> (4 * i)) & 15; };
         typename B::Ctx c;
@@ -380,12 +396,29 @@ struct SceneSim : Sim<M> {
                 });
             });
         }
-        for (int i = 0; i < ns; ++i) {
-            float R[9];
-            quat2mat(SP.static_quat[i], R);
-            sfor<9>([&](auto K) MI_LAMBDA { W(W_RS, 9 * i + K) = R[K]; });
-            sfor<3>([&](auto K) MI_LAMBDA { W(W_XST, 3 * i + K) = SP.static_pos[i][K] - root[K]; W(W_HS, 3 * i + K) = SP.static_half[i][K]; });
+        if constexpr (!WIDE) {
+            for (int i = 0; i < ns; ++i) {
+                float R[9];
+                quat2mat(SP.static_quat[i], R);
+                sfor<9>([&](auto K) MI_LAMBDA { W(W_RS, 9 * i + K) = R[K]; });
+                sfor<3>([&](auto K) MI_LAMBDA { W(W_XST, 3 * i + K) = SP.static_pos[i][K] - root[K]; W(W_HS, 3 * i + K) = SP.static_half[i][K]; });
+            }
+        } else {
+            // the block's entries by COMPILE-TIME index (a run-time index into a kernel argument sends the whole argument through scratch memory: the
+            // note at W_VB above); ns is wave-uniform
+            sfor<NSTAT>([&](auto I_) MI_LAMBDA {
+                constexpr int i = I_;
+                if (i < ns) {
+                    float R[9];
+                    quat2mat(SX->quat[i], R);
+                    sfor<9>([&](auto K) MI_LAMBDA { W(W_RS, 9 * i + K) = R[K]; });
+                    sfor<3>([&](auto K) MI_LAMBDA { W(W_XST, 3 * i + K) = SX->pos[i][K] - root[K]; W(W_HS, 3 * i + K) = SX->half[i][K]; });
+                    W(W_MUS, i) = SX->mu[i];
+                }
+            });
         }
+        // friction of static box j: the work area (wide form) or SceneParams -- WIDE is a constant, the other operand is never compiled in
+#define MI_STATIC_MU(j) (WIDE ? W(W_MUS, (j)) : SP.static_mu[(j)])
         MI_PHASE();
         // ------------------------------------------------------------ joint limit rows (as core/engine.hpp)
         sfor<ND>([&](auto D) MI_LAMBDA {
@@ -559,7 +592,7 @@ struct SceneSim : Sim<M> {
                         cb[(S_AUX + 10) * ST] = __builtin_bit_cast(float, fid);
                         sfor<3>([&](auto I_) MI_LAMBDA { cb[(S_GEO + I_) * ST] = fr[0][I_]; cb[(S_GEO + 3 + I_) * ST] = pc[I_]; });
                         cb[(S_AUX + 3) * ST] = target_velocity(dist);
-                        cb[(S_AUX + 7) * ST] = 0.5f * (SP.arm_mu + (fr_ ? SP.free_mu[ib] : SP.static_mu[ib]));
+                        cb[(S_AUX + 7) * ST] = 0.5f * (SP.arm_mu + (fr_ ? SP.free_mu[ib] : MI_STATIC_MU(ib)));
                         cb[(S_AUX + 8) * ST] = __builtin_bit_cast(float, (int)-1);
                         cb[(S_AUX + 9) * ST] = __builtin_bit_cast(float, fr_ ? ib : (int)-1);
                         cnt += 1;
@@ -575,7 +608,7 @@ struct SceneSim : Sim<M> {
         int nbox = 0;
         // broad phase of the box pairs (round 6): bit (i * NTGT + t) -- free box i and target t (static boxes first, then the free ones) -- is set when
         // their bounding spheres come within contact_offset; the corner, edge and outline tests below skip the other pairs (conservative: same contacts)
-        unsigned pmask = 0u;
+        PMask pmask = 0u;
         for (int i = 0; i < nf; ++i) {
             float xi[3];
             ld3(W_XF, i, xi);
@@ -595,7 +628,7 @@ struct SceneSim : Sim<M> {
                 const int shj = st_ ? 0 : shape_of(j);
                 const float rj = (shj != 0) ? ((shj == 2 ? hj[0] : 0.f) + hj[1]) : MI_SQRT(dot3(hj, hj));
                 const float reach = ri + rj + P.contact_offset + 1e-4f;
-                pmask |= (dot3(d, d) < reach * reach) ? (1u << (i * NTGT + t)) : 0u;
+                pmask |= (dot3(d, d) < reach * reach) ? (PMask(1) << (i * NTGT + t)) : PMask(0);
             }
         }
         for (int i = 0; i < nf; ++i) {
@@ -632,7 +665,7 @@ struct SceneSim : Sim<M> {
                         matTvec3(Rb_, rel, cl);
                         scene_sphere_box(cl, 0.f, hb_, &dist, nl);
                         matvec3(Rb_, nl, n);
-                        mu_b = st_ ? SP.static_mu[j] : SP.free_mu[j];
+                        mu_b = st_ ? MI_STATIC_MU(j) : SP.free_mu[j];
                         ib = st_ ? -1 : j;
                     }
                     if (!(dist < P.contact_offset)) continue;
@@ -690,7 +723,7 @@ struct SceneSim : Sim<M> {
         };
         // the corners of the STATIC boxes inside free boxes (a plate lying on a stand smaller than itself has no corner of its own in the stand):
         // the free box is pushed back along the inward normal of the face the corner is nearest to
-        constexpr int FID_SC = 1 + NSPH * NTGT + kSceneMaxFree * 8 * (NTGT + 1), FID_EE = FID_SC + kSceneMaxStatic * 8 * kSceneMaxFree,
+        constexpr int FID_SC = 1 + NSPH * NTGT + kSceneMaxFree * 8 * (NTGT + 1), FID_EE = FID_SC + NSTAT * 8 * kSceneMaxFree,
                       FID_FC = FID_EE + kSceneMaxFree * NTGT * 9, FID_RD = FID_FC + kSceneMaxFree * NTGT * 8,
                       FID_END = FID_RD + kSceneMaxFree * (NTGT + 1) * 4;
         static_assert(FID_END < (1 << 23), "feature ids are small positive integers (carried as the bit patterns of denormal floats: copied, never computed with)");
@@ -720,7 +753,7 @@ struct SceneSim : Sim<M> {
                     if (nbox >= KBOX) { refused += 1; continue; }
                     matvec3(Rb_, nl, n);
                     sfor<3>([&](auto K) MI_LAMBDA { n[K] = -n[K]; });
-                    add_box_contact(j, -1, n, pc, dist, 0.5f * (SP.free_mu[j] + SP.static_mu[t]), FID_SC + (t * 8 + cr) * kSceneMaxFree + j);
+                    add_box_contact(j, -1, n, pc, dist, 0.5f * (SP.free_mu[j] + MI_STATIC_MU(t)), FID_SC + (t * 8 + cr) * kSceneMaxFree + j);
                 }
             }
         }
@@ -746,8 +779,8 @@ struct SceneSim : Sim<M> {
                 ld3(st_ ? W_HS : W_HF, j, hj);
                 const int kind = scene_box_edge(Ri, xi, hi_, Rb_, xb_, hj, P.contact_offset, &dist_, n_, pc_, &axes);
                 if (kind == 0) continue;
-                const float mu_ = 0.5f * (SP.free_mu[i] + (st_ ? SP.static_mu[j] : SP.free_mu[j]));
-                const int pair = i * NTGT + (st_ ? j : kSceneMaxStatic + j);
+                const float mu_ = 0.5f * (SP.free_mu[i] + (st_ ? MI_STATIC_MU(j) : SP.free_mu[j]));
+                const int pair = i * NTGT + (st_ ? j : NSTAT + j);
                 if (kind == 1) {
                     if (!(dist_ < P.contact_offset)) continue;
                     if (nbox >= KBOX) { refused += 1; continue; }
@@ -791,7 +824,7 @@ struct SceneSim : Sim<M> {
                     ld9(st_ ? W_RS : W_RF, j, Rb_);
                     ld3(st_ ? W_XST : W_XF, j, xb_);
                     ld3(st_ ? W_HS : W_HF, j, hb_);
-                    mu_b = st_ ? SP.static_mu[j] : SP.free_mu[j];
+                    mu_b = st_ ? MI_STATIC_MU(j) : SP.free_mu[j];
                     const float rel[3] = {xi[0] - xb_[0], xi[1] - xb_[1], xi[2] - xb_[2]};
                     if (shj == 0) {             // the segment in the box's frame
                         matTvec3(Rb_, rel, c0);
@@ -853,11 +886,13 @@ struct SceneSim : Sim<M> {
                     if (!ok || !(dist < P.contact_offset)) continue;
                     if (nbox >= KBOX) { refused += 1; continue; }
                     const float pc[3] = {pa[0] - r * n[0], pa[1] - r * n[1], pa[2] - r * n[2]};
-                    const int tt = (t < 0) ? 0 : (st_ ? 1 + j : 1 + kSceneMaxStatic + j);
+                    const int tt = (t < 0) ? 0 : (st_ ? 1 + j : 1 + NSTAT + j);
                     add_box_contact(i, (t >= ns) ? j : -1, n, pc, dist, 0.5f * (SP.free_mu[i] + mu_b), FID_RD + ((i * (NTGT + 1) + tt) * 4 + e));
                 }
             }
         }
+#undef MI_STATIC_MU      // (defined at the head of the narrow phase, after the work area is filled: a macro, not a lambda or a helper function -- either
+                         //  changed the capacity-4 kernel's SGPR spills, profiles/scene_wide_statics.md; nothing below this line reads a static's friction)
         *ncontact = (narm + nbox) | (refused << 16);
         MI_PHASE();
         // ------------------------------------------------------------ projected Gauss-Seidel sweeps: limits, actor contacts, box contacts

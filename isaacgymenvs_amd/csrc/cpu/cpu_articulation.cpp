@@ -7,7 +7,7 @@
 using AM = ModelArticulation;
 static_assert(sizeof(MiArticulationParams) == sizeof(ArticulationParams), "MiArticulationParams layout");
 
-ArticulationMeta mi_articulation_meta() { return ArticulationMeta{AM::ND, AM::NB, AM::NSENS, AM::NSPH, AM::FIXED}; }
+ArticulationMeta mi_articulation_meta() { return ArticulationMeta{AM::ND, AM::NB, AM::NSENS, AM::NSPH, AM::FIXED, kSceneStaticCap}; }
 
 int cpu_articulation_reset(MiEngine* e, const int64_t* ids, int n) {
     const ArticulationParams& p = e->artic;
@@ -23,7 +23,7 @@ static int scene_simulate(MiEngine* e, const ArticulationParams& p) {
         for (int en = 0; en < v.N; ++en) {
             float rows[SceneRows<M>::value];
             for (int ss = 0; ss < e->P.substeps; ++ss)
-                articulation_scene_substep_env<M>(v, e->P, p, en, RowStore<1>{rows}, Strided{v.scene_warm + en, v.N});
+                articulation_scene_substep_env<M>(v, e->P, p, en, RowStore<1>{rows}, Strided{v.scene_warm + en, v.N}, kSceneStaticCap > kSceneMaxStatic ? &e->statics : nullptr);
         }
         return 0;
     } else {

@@ -71,6 +71,9 @@ extern "C" int mi_engine_set_terrain(MiEngine* e, const int16_t* height_samples,
                      env_length, max_init_level);
     return 0;
 }
+extern "C" int mi_engine_set_scene_statics(MiEngine* e, int n, const float* pos, const float* quat, const float* half, const float* mu) {
+    return result(core_set_scene_statics(e, n, pos, quat, half, mu));
+}
 static int hand_call(MiEngine* e, int what, const float* actions, bool simulate_only, const int64_t* ids, int n, float* out_j, float* out_h) {
     const bool sh = e->task == T_SHADOWHAND;
     switch (what) {

@@ -47,6 +47,7 @@ struct EngineCore {
     HandParams hand;
     HandView hv;
     ArticulationParams artic;
+    SceneStatics statics;   // the Articulation scene's static boxes as a wide-capacity library reads them (mi_engine_set_scene_statics; default: artic.scene's)
     int max_init_level;
     View v;
     float clip_obs;
@@ -86,6 +87,55 @@ inline size_t core_arena_bytes(const char* task, int num_envs) {
     build_layout(t, num_envs, L, nullptr, nullptr);
     core_task_layout(t, num_envs, L, nullptr, nullptr);
     return L.off;
+}
+
+// the engine's static set as mi_engine_create leaves it: MiScene.static_* (at most MI_SCENE_MAX_STATIC boxes)
+inline void core_default_statics(EngineCore& e) {
+    const SceneParams& sc = e.artic.scene;
+    e.statics = SceneStatics{};
+    e.statics.n = sc.n_static < 0 ? 0 : (sc.n_static < kSceneMaxStatic ? sc.n_static : kSceneMaxStatic);
+    for (int i = 0; i < e.statics.n; ++i) {
+        for (int k = 0; k < 3; ++k) { e.statics.pos[i][k] = sc.static_pos[i][k]; e.statics.half[i][k] = sc.static_half[i][k]; }
+        for (int k = 0; k < 4; ++k) e.statics.quat[i][k] = sc.static_quat[i][k];
+        e.statics.mu[i] = sc.static_mu[i];
+    }
+}
+// static boxes the scene form of this library's Articulation unit holds (MI_SCENE_MAX_STATIC, or MI_SCENE_MAX_STATIC_WIDE for a variant built wide)
+inline int core_scene_static_capacity() { const int c = mi_articulation_meta().static_cap; return c > 0 ? c : kSceneMaxStatic; }
+// mi_engine_set_scene_statics: replaces the engine's whole static set.  Host only: the next sub-step launch carries the new set.  The first
+// MI_SCENE_MAX_STATIC boxes are mirrored into artic.scene (what a capacity-4 library simulates, and what anything that reads MiScene sees).
+inline std::string core_set_scene_statics(EngineCore* e, int n, const float* pos, const float* quat, const float* half, const float* mu) {
+    if (!e) return "null engine";
+    if (e->task != T_ARTICULATION || !mi_articulation_meta().fixed)
+        return "mi_engine_set_scene_statics: only a fixed-base Articulation engine has a scene";
+    const int cap = core_scene_static_capacity();
+    if (n < 0) return "mi_engine_set_scene_statics: n < 0";
+    if (n > cap) return "mi_engine_set_scene_statics: " + std::to_string(n) + " static boxes, this library's scene holds " + std::to_string(cap) +
+                        " (capacity " + std::to_string(MI_SCENE_MAX_STATIC_WIDE) + ": a variant built with MI_SCENE_STATIC_CAP=" + std::to_string(MI_SCENE_MAX_STATIC_WIDE) + ")";
+    if (n > 0 && (!pos || !quat || !half || !mu)) return "mi_engine_set_scene_statics: null array with n > 0";
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k)
+            if (!(half[3 * i + k] > 0.f)) return "mi_engine_set_scene_statics: static box " + std::to_string(i) + " has a non-positive half size";
+        double q2 = 0;
+        for (int k = 0; k < 4; ++k) q2 += (double)quat[4 * i + k] * quat[4 * i + k];
+        if (!(std::fabs(std::sqrt(q2) - 1.0) <= 1e-3)) return "mi_engine_set_scene_statics: static box " + std::to_string(i) + " has a quaternion that is not of unit norm";
+    }
+    SceneStatics st{};
+    st.n = n;
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) { st.pos[i][k] = pos[3 * i + k]; st.half[i][k] = half[3 * i + k]; }
+        for (int k = 0; k < 4; ++k) st.quat[i][k] = quat[4 * i + k];
+        st.mu[i] = mu[i];
+    }
+    e->statics = st;
+    SceneParams& sc = e->artic.scene;
+    sc.n_static = n < kSceneMaxStatic ? n : kSceneMaxStatic;
+    for (int i = 0; i < kSceneMaxStatic; ++i) {
+        for (int k = 0; k < 3; ++k) { sc.static_pos[i][k] = i < n ? st.pos[i][k] : 0.f; sc.static_half[i][k] = i < n ? st.half[i][k] : 0.f; }
+        for (int k = 0; k < 4; ++k) sc.static_quat[i][k] = i < n ? st.quat[i][k] : 0.f;
+        sc.static_mu[i] = i < n ? st.mu[i] : 0.f;
+    }
+    return {};
 }
 
 inline const char* core_check_hand(int t, const HandParams& hp) {
@@ -138,6 +188,7 @@ inline std::string core_create(EngineCore& e, const char* task, const MiSimParam
         memcpy(&e.artic, task_params, sizeof(ArticulationParams));
         if (!scene_shapes_known(e.artic.scene.n_free, e.artic.scene.free_shape))
             return "mi_engine_create: MiScene.free_shape holds an unknown shape code (0 box, 1 sphere, 2 capsule)";
+        core_default_statics(e);
     } else memcpy(&e.loco, task_params, sizeof(LocoParams));
     Layout L;
     build_layout(t, num_envs, L, &e.v, (char*)arena, is_hand_task(t) ? e.hand.num_obs : 0);
@@ -246,6 +297,9 @@ static const EngineOption kCoreOptions[] = {
          e.v.actor_scale = x != 0 ? e.actor_scale_arena : nullptr;
          e.v.limit_shift = x != 0 ? e.limit_shift_arena : nullptr; return {}; },
      MI_GET { return (is_hand_task(e.task) || e.v.actor_scale != nullptr) ? 1.0 : 0.0; }},
+    // static boxes the scene of this library's Articulation unit holds: 4, or 12 for a variant built wide (read-only)
+    {"scene_static_capacity", MI_ON_BOTH, MI_SET { (void)e; (void)x; return "scene_static_capacity: read-only (a build property of the library)"; },
+     MI_GET { return e.task == T_ARTICULATION ? core_scene_static_capacity() : 0; }},
     // terrain.slopeTreshold of the mesh generator (anymal_terrain.py:576); 0 = off
     {"terrain_slope_threshold", MI_ON_BOTH, MI_SET {
          if (e.task != T_ANYMAL) return "terrain_slope_threshold: only AnymalTerrain has a terrain";

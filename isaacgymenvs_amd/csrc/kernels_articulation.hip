@@ -9,7 +9,7 @@
 #include "gen/model_articulation.h"
 #include "tasks/articulation.hpp"
 
-ArticulationMeta mi_articulation_meta() { return ArticulationMeta{ModelArticulation::ND, ModelArticulation::NB, ModelArticulation::NSENS, ModelArticulation::NSPH, ModelArticulation::FIXED}; }
+ArticulationMeta mi_articulation_meta() { return ArticulationMeta{ModelArticulation::ND, ModelArticulation::NB, ModelArticulation::NSENS, ModelArticulation::NSPH, ModelArticulation::FIXED, mi::kSceneStaticCap}; }
 
 namespace mi {
 
@@ -48,6 +48,9 @@ constexpr int SCENE_LANES_MAX = ((size_t)(SCENE_ROWS + SCENE_WARM) * 8 * sizeof(
 // 0.97 / 2.31 / 7.86 -- a wavefront with ONE env is slower than one with eight once every SIMD has one: the wavefronts do not wait for each
 // other's divergent loops, they compete for instruction fetch (the kernel holds the whole register file, one wavefront per SIMD, and its code is far
 // larger than the instruction cache).
+// (Two kernel texts, one per capacity, and only one of them in a build: the capacity-4 kernel below is the text it had before the wide form existed,
+//  which is what keeps its registers, scratch and spills where they were -- profiles/scene_wide_statics.md.)
+#if MI_SCENE_STATIC_CAP <= 4
 template <int LANES>
 __global__ __launch_bounds__(64) void articulation_scene_substep_kernel(View v, SimParams P, ArticulationParams p) {
     extern __shared__ float lds_scene[];
@@ -62,6 +65,26 @@ __global__ __launch_bounds__(64) void articulation_scene_substep_kernel(View v, 
         for (int k = 0; k < SCENE_WARM; ++k) v.scene_warm[(size_t)k * N + e] = warm[k * LANES];
     }
 }
+#else
+// The WIDE form (a variant built with -DMI_SCENE_STATIC_CAP=12, assets/runtime.py): up to 12 static boxes, which arrive BY VALUE as one more kernel
+// argument (532 B) and are copied into the LDS work area with compile-time indices at the head of the sub-step (core/scene_engine.hpp).  The only scene
+// kernel of such a library -- no library carries the sub-step's code twice.
+static_assert(sizeof(View) + sizeof(SimParams) + sizeof(ArticulationParams) + sizeof(SceneStatics) <= 4096, "the wide scene kernel's arguments fit the 4 KB kernarg segment");
+template <int LANES>
+__global__ __launch_bounds__(64) void articulation_scene_substep_kernel(View v, SimParams P, ArticulationParams p, SceneStatics sx) {
+    extern __shared__ float lds_scene[];
+    const int e = blockIdx.x * LANES + threadIdx.x;
+    if (e >= v.N) return;
+    if constexpr (AM::FIXED == 1) {
+        float* rows = lds_scene + threadIdx.x;
+        float* warm = lds_scene + SCENE_ROWS * LANES + threadIdx.x;
+        const int N = v.N;
+        for (int k = 0; k < SCENE_WARM; ++k) warm[k * LANES] = v.scene_warm[(size_t)k * N + e];
+        articulation_scene_substep_env<AM>(v, P, p, e, RowStore<LANES>{rows}, Strided{warm, LANES}, &sx);
+        for (int k = 0; k < SCENE_WARM; ++k) v.scene_warm[(size_t)k * N + e] = warm[k * LANES];
+    }
+}
+#endif
 __global__ void articulation_reset_kernel(View v, ArticulationParams p, const long long* __restrict__ ids, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (ids ? n : v.N)) return;
@@ -126,7 +149,7 @@ static int scene_lanes(const int N) {
     if (lanes != 4 && lanes != 8) lanes = 8;
     return lanes > SCENE_LANES_MAX ? SCENE_LANES_MAX : lanes;
 }
-hipError_t launch_simulate_articulation(const View& v, const SimParams& P, const ArticulationParams& p, hipStream_t s) {
+hipError_t launch_simulate_articulation(const View& v, const SimParams& P, const ArticulationParams& p, const SceneStatics& sx, hipStream_t s) {
     if (articulation_has_scene(p)) {
         if (AM::FIXED != 1) return hipErrorInvalidValue;
         static_assert((size_t)(SCENE_ROWS + SCENE_WARM) * SCENE_LANES_MAX * sizeof(float) <= 160 * 1024, "the scene's row store of one workgroup fits the LDS of a CU");
@@ -140,8 +163,13 @@ hipError_t launch_simulate_articulation(const View& v, const SimParams& P, const
                     static unsigned long long scene_configured = 0ull;
                     err = ensure_dynamic_lds((const void*)articulation_scene_substep_kernel<LANES>, lds, &scene_configured);
                     if (err != hipSuccess) return;
-                    for (int i = 0; i < P.substeps; ++i)
+                    for (int i = 0; i < P.substeps; ++i) {
+#if MI_SCENE_STATIC_CAP <= 4
                         hipLaunchKernelGGL(articulation_scene_substep_kernel<LANES>, dim3((v.N + LANES - 1) / LANES), dim3(LANES), lds, s, v, P, p);
+#else
+                        hipLaunchKernelGGL(articulation_scene_substep_kernel<LANES>, dim3((v.N + LANES - 1) / LANES), dim3(LANES), lds, s, v, P, p, sx);
+#endif
+                    }
                 }
             }
         });

@@ -190,7 +190,7 @@ hipError_t launch_simulate_ball_balance(const View& v, const BbotView& bv, const
 hipError_t launch_init_ball_balance(const View& v, const BbotView& bv, const BallBalanceParams& p, hipStream_t s);
 hipError_t launch_reset_ball_balance(const View& v, const BbotView& bv, const BallBalanceParams& p, const long long* ids, int n, hipStream_t s);
 // kernels_articulation.hip (the one translation unit that holds the run-time-compiled robot)
-hipError_t launch_simulate_articulation(const View& v, const SimParams& P, const ArticulationParams& p, hipStream_t s);
+hipError_t launch_simulate_articulation(const View& v, const SimParams& P, const ArticulationParams& p, const SceneStatics& sx, hipStream_t s);
 hipError_t launch_reset_articulation(const View& v, const ArticulationParams& p, const long long* ids, int n, hipStream_t s);
 hipError_t launch_body_states_articulation(const View& v, hipStream_t s);
 hipError_t launch_kinematics_articulation(const View& v, const SimParams& P, float* out_j, float* out_h, hipStream_t s);
@@ -370,7 +370,7 @@ extern "C" int mi_engine_simulate(MiEngine* e, void* stream) {
         case T_QUADCOPTER: HIP_OK(launch_simulate_quadcopter(e->v, e->qv, e->P, e->quad, s)); break;
         case T_INGENUITY: HIP_OK(launch_simulate_ingenuity(e->v, e->iv, e->P, e->ing, s)); break;
         case T_BALLBALANCE: HIP_OK(launch_simulate_ball_balance(e->v, e->bv, e->P, e->bbot, s)); break;
-        case T_ARTICULATION: HIP_OK(launch_simulate_articulation(e->v, e->P, e->artic, s)); break;
+        case T_ARTICULATION: HIP_OK(launch_simulate_articulation(e->v, e->P, e->artic, e->statics, s)); break;
     }
     return 0;
 }
@@ -432,6 +432,11 @@ extern "C" int mi_engine_set_terrain(MiEngine* e, const int16_t* height_samples,
     core_set_terrain(*e, (const short*)height_samples, rows, cols, horizontal_scale, vertical_scale, border_size, env_origins, num_levels, num_terrains,
                      env_length, max_init_level);
     return 0;
+}
+
+// host only, like mi_engine_set_terrain: the next mi_engine_simulate carries the new set (a wide-capacity library passes it as a kernel argument)
+extern "C" int mi_engine_set_scene_statics(MiEngine* e, int n, const float* pos, const float* quat, const float* half, const float* mu) {
+    return result(core_set_scene_statics(e, n, pos, quat, half, mu));
 }
 
 extern "C" int mi_compute_locomotion_observations(const char* task, int n, const MiLocoParams* p, const float* root_states,

@@ -11,6 +11,15 @@ namespace mi {
 // one set of scene sizes for the C ABI (include/mi_engine.h), the arena layout, the kernels and the reset code
 static_assert(kSceneMaxFree == MI_SCENE_MAX_FREE && kSceneMaxStatic == MI_SCENE_MAX_STATIC, "core/scene_engine.hpp and include/mi_engine.h agree on the scene sizes");
 
+static_assert(kSceneMaxStaticWide == MI_SCENE_MAX_STATIC_WIDE, "core/scene_engine.hpp and include/mi_engine.h agree on the wide static capacity");
+// Static capacity of the scene form THIS build of the run-time robot's translation unit carries: a build define of the variant (assets/runtime.py),
+// absent = 4.  One capacity per library: the scene sub-step's code already outgrows the instruction cache, no library carries it twice.
+#ifndef MI_SCENE_STATIC_CAP
+#define MI_SCENE_STATIC_CAP 4
+#endif
+constexpr int kSceneStaticCap = MI_SCENE_STATIC_CAP;
+static_assert(kSceneStaticCap == kSceneMaxStatic || kSceneStaticCap == kSceneMaxStaticWide, "MI_SCENE_STATIC_CAP: 4 or 12");
+
 struct ArticulationParams {   // mirrors MiArticulationParams (include/mi_engine.h)
     float kp[kMaxDof], kd[kMaxDof];
     float max_angular_velocity;
@@ -30,12 +39,14 @@ static inline bool scene_shapes_known(const int n_free, const int free_shape) {
 }
 // floats of the scene form's row store (1 for a floating-base robot, which has no scene form: SceneSim<M> is never instantiated for it)
 template <class M, bool F = (M::FIXED == 1)> struct SceneRows { static constexpr int value = 1; };
-template <class M> struct SceneRows<M, true> { static constexpr int value = SceneSim<M>::ROW_SLOTS; };
+template <class M> struct SceneRows<M, true> { static constexpr int value = SceneSim<M, kSceneStaticCap>::ROW_SLOTS; };
+// sx: the static boxes of a wide-capacity build (null, and never read, at capacity 4: the statics are p.scene.static_*)
 template <class M, int RS>
-MI_HD void articulation_scene_substep_env(const View& v, const SimParams& P, const ArticulationParams& p, const int e, const RowStore<RS> rows, const Strided warm) {
+MI_HD void articulation_scene_substep_env(const View& v, const SimParams& P, const ArticulationParams& p, const int e, const RowStore<RS> rows, const Strided warm,
+                                          const SceneStatics* sx = nullptr) {
     constexpr int ND = M::ND;
     const int N = v.N;
-    SceneSim<M> sim;
+    SceneSim<M, kSceneStaticCap> sim;
     sfor<13>([&](auto K) MI_LAMBDA { sim.root[K] = v.root[K * N + e]; });
     float tau[M::NDA], target[M::NDA], kp[M::NDA], kd[M::NDA], vmax[M::NDA];
     sfor<ND>([&](auto K) MI_LAMBDA {
@@ -58,7 +69,7 @@ MI_HD void articulation_scene_substep_env(const View& v, const SimParams& P, con
     drv.kpv = kp; drv.kdv = kd;
     const float h = P.dt / (float)P.substeps;
     int nc = 0;
-    sim.substep_scene(P, p.scene, tau, drv, h, rows, Strided{v.laml + e, N}, Strided{v.dof_force + e, N}, &nc, warm, vmax, Strided{v.netf + e, N});
+    sim.substep_scene(P, p.scene, tau, drv, h, rows, Strided{v.laml + e, N}, Strided{v.dof_force + e, N}, &nc, warm, vmax, Strided{v.netf + e, N}, sx);
     v.scene_nc[e] = nc & 0xFFFF;
     v.scene_nc[N + e] += nc >> 16;
     sfor<ND>([&](auto K) MI_LAMBDA { v.dof[K * N + e] = sim.q[K]; v.dof[(ND + K) * N + e] = sim.qd[K]; });

@@ -39,7 +39,8 @@ MI_MAX_DOF = 32
 # include/mi_engine.h MI_ABI_VERSION: bumped whenever the arena layout, a parameter struct or an export changes (2: round 4 -- cumulative
 # episode statistics tensors, per-body actor scales, rigid_body_state; 3: round 5 -- compensated cumulative statistics (episode_cum_stats [32],
 # reward_workspace [8]), hand_pair_count, hand_body_mass_scale; 4: round 5, scenes -- MiArticulationParams.scene / drive_vmax, scene_state, scene_contacts,
-# scene_warm).  A library of another version is refused when it is loaded, and a state
+# scene_warm).  Additive exports that leave every struct and the arena as they are do NOT bump the version (mi_engine_set_scene_statics and the
+# read-only option scene_static_capacity: a client that never calls them sees no difference).  A library of another version is refused when it is loaded, and a state
 # checkpoint (VecTask.get_env_state) carries the version + arena size it was taken with.
 MI_ABI_VERSION = 4
 
@@ -147,6 +148,7 @@ class MiBallBalanceParams(C.Structure):
 
 
 MI_SCENE_MAX_FREE, MI_SCENE_MAX_STATIC = 4, 4
+MI_SCENE_MAX_STATIC_WIDE = 12       # a variant whose Articulation unit was built with -DMI_SCENE_STATIC_CAP=12 (assets/runtime.py variant_library)
 MI_SHAPE_BOX, MI_SHAPE_SPHERE, MI_SHAPE_CAPSULE = 0, 1, 2
 
 
@@ -228,6 +230,7 @@ class MiTensorDesc(C.Structure):
 EXPORTS = ["mi_abi_version", "mi_task_info", "mi_engine_arena_bytes", "mi_engine_create", "mi_engine_init_state",
            "mi_engine_destroy", "mi_engine_num_tensors", "mi_engine_tensor_desc", "mi_engine_step",
            "mi_engine_reset_idx", "mi_engine_simulate", "mi_engine_refresh_rigid_body_states", "mi_engine_compute_jacobians", "mi_engine_compute_mass_matrices", "mi_engine_set_option", "mi_engine_get_option", "mi_engine_set_noise", "mi_engine_last_ring", "mi_engine_set_terrain",
+           "mi_engine_set_scene_statics",
            "mi_compute_locomotion_observations", "mi_compute_locomotion_reward", "mi_compute_cartpole_reward",
            "mi_compute_hand_reward", "mi_compute_hand_full_state", "mi_randomize_rotation",
            "mi_compute_anymal_observations", "mi_compute_anymal_reward", "mi_compute_quadcopter_reward",
@@ -463,6 +466,7 @@ def _bind_lifecycle(L):
     L.mi_engine_last_ring.argtypes = [C.c_void_p]
     L.mi_engine_set_terrain.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                         C.c_int, C.c_int, C.c_float, C.c_int]
+    L.mi_engine_set_scene_statics.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 
@@ -790,6 +794,13 @@ class Engine:
         p = MiNoiseParams(dist={"off": 0, "gaussian": 1, "uniform": 2}[dist], op={"additive": 0, "scaling": 1}[op], a=a, b=b,
                           a_corr=a_corr, b_corr=b_corr, epoch=epoch)
         check(self.L.mi_engine_set_noise(self.h, int(which), C.byref(p)), self.L)
+
+    def set_scene_statics(self, statics):
+        """mi_engine_set_scene_statics: the scene's whole static set, a list of dicts pos [3] / quat [4] xyzw / half [3] / mu (at most the
+        library's "scene_static_capacity")"""
+        n = len(statics)
+        flat = lambda key, w: (C.c_float * max(1, n * w))(*[float(x) for s in statics for x in (s[key] if w > 1 else [s[key]])])      # noqa: E731
+        check(self.L.mi_engine_set_scene_statics(self.h, n, flat("pos", 3), flat("quat", 4), flat("half", 3), flat("mu", 1)), self.L)
 
     def get_option(self, key):
         out = C.c_double()

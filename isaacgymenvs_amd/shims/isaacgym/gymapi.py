@@ -276,6 +276,36 @@ class _ActuatorProps:
         self.kp = self.kv = 0.0
 
 
+def _ring_wall_boxes(V, k):
+    """A hollow mesh (vertices V [n, 3], the ring's axis the vertical through the middle of their bounding box) cut into k equal angular sectors,
+    one box per sector, tangent to the ring at the sector's middle: the inner face at the smallest inner radius among the sector's vertices (it
+    never reaches into the arena), the outer face at their largest radius, the height their z range, the width (2 r_out tan(pi / k)) meeting the
+    neighbours at the outer radius.  -> ([dict(pos[3], yaw, half[3])] in the mesh's frame, the worst distance of a vertex to its sector's box:
+    the flat inner faces stand off the round inner surface by up to r_in (1 - cos(pi / k)))."""
+    V = np.asarray(V, float)
+    c = 0.5 * (V.min(0) + V.max(0))
+    d = V[:, :2] - c[:2]
+    r, phi = np.hypot(d[:, 0], d[:, 1]), np.mod(np.arctan2(d[:, 1], d[:, 0]), 2 * np.pi)
+    sec = np.minimum((phi / (2 * np.pi / k)).astype(int), k - 1)
+    mid = 0.5 * (r.min() + r.max())                      # inner surface | outer surface
+    boxes, gap = [], 0.0
+    for s in range(k):
+        m = sec == s
+        if not (m & (r < mid)).any() or not (m & (r >= mid)).any():
+            raise NotImplementedError(f"MI_SHIM_RING_WALLS={k}: sector {s} of the ring holds no vertex of its inner or of its outer surface")
+        r_in, r_out = float(r[m & (r < mid)].min()), float(r[m].max())
+        z0, z1 = float(V[m, 2].min()), float(V[m, 2].max())
+        th = 2 * np.pi * (s + 0.5) / k
+        u, t = np.array([np.cos(th), np.sin(th)]), np.array([-np.sin(th), np.cos(th)])
+        half = np.array([0.5 * (r_out - r_in), r_out * np.tan(np.pi / k), 0.5 * (z1 - z0)])
+        pos = np.array([c[0] + 0.5 * (r_in + r_out) * u[0], c[1] + 0.5 * (r_in + r_out) * u[1], 0.5 * (z0 + z1)])
+        loc = np.stack([d[m] @ u - 0.5 * (r_in + r_out), d[m] @ t, V[m, 2] - pos[2]], axis=1)
+        out = np.maximum(np.abs(loc) - half, 0.0)
+        gap = max(gap, float(np.sqrt((out * out).sum(1)).max()))
+        boxes.append(dict(pos=[float(x) for x in pos], yaw=float(th), half=[float(x) for x in half]))
+    return boxes, gap
+
+
 def _single_box_urdf(path):
     """A URDF that is ONE rigid body -- no joint that moves, one link with collision geometry -- read as a box: what the reference's table-top
     tasks load their objects and stages from (trifinger.py:1169-1255: table_without_border.urdf, cube_multicolor_rrc.urdf; `create_box` is the
@@ -304,7 +334,7 @@ def _single_box_urdf(path):
     pos = _floats(org.get("xyz", "0 0 0"), 3) if org is not None else np.zeros(3)
     quat = rpy_to_quat(*_floats(org.get("rpy", "0 0 0"), 3)) if org is not None else np.array([0.0, 0.0, 0.0, 1.0])
     g = geo[0]
-    hollow = False
+    hollow, ring_v, ring_org = False, None, None
     if g.tag == "box":
         dims, mesh = _floats(g.get("size"), 3), False
     elif g.tag == "mesh":
@@ -325,6 +355,7 @@ def _single_box_urdf(path):
         d1 = T[:, 1, 0] * T[:, 2, 1] - T[:, 1, 1] * T[:, 2, 0]
         d2 = T[:, 2, 0] * T[:, 0, 1] - T[:, 2, 1] * T[:, 0, 0]
         hollow = not bool((((d0 >= 0) & (d1 >= 0) & (d2 >= 0)) | ((d0 <= 0) & (d1 <= 0) & (d2 <= 0))).any())
+        ring_v, ring_org = (V, (pos.copy(), np.asarray(quat, float).copy())) if hollow else (None, None)
         pos = pos + quat_to_mat(quat) @ (0.5 * (lo + hi))
     else:
         return None
@@ -336,7 +367,7 @@ def _single_box_urdf(path):
         if it is not None and all(abs(float(it.get(k, 0.0))) < 1e-12 for k in ("ixy", "ixz", "iyz")):
             inertia = [float(it.get(k)) for k in ("ixx", "iyy", "izz")]
     return dict(link=ln.get("name"), dims=[float(d) for d in dims], pos=[float(x) for x in pos], quat=[float(x) for x in quat],
-                mass=mass if (mass is not None and mass > 0) else None, inertia=inertia, mesh=mesh, hollow=hollow)
+                mass=mass if (mass is not None and mass > 0) else None, inertia=inertia, mesh=mesh, hollow=hollow, ring_v=ring_v, ring_org=ring_org)
 
 
 def _scene_body(a):
@@ -396,7 +427,20 @@ class _Asset:
         if box is not None:
             # one rigid body: a box actor of a scene, like gym.create_box's (static with fix_base_link, else free)
             import warnings
-            if box["hollow"]:
+            self.ring_boxes = None                 # MI_SHIM_RING_WALLS=K: the K wall boxes of a hollow mesh, poses in the link frame
+            ring_k = int(os.environ.get("MI_SHIM_RING_WALLS", "0") or 0)
+            if box["hollow"] and ring_k != 0:
+                if not 4 <= ring_k <= 11:
+                    raise ValueError(f"MI_SHIM_RING_WALLS={ring_k}: 4 to 11 wall boxes (a scene holds 12 static boxes), or 0 / unset for none")
+                from ...assets.model import quat_mul, quat_to_mat
+                walls, gap = _ring_wall_boxes(box["ring_v"], ring_k)
+                o_p, o_q = box["ring_org"]
+                self.ring_boxes = [dict(pos=[float(x) for x in o_p + quat_to_mat(o_q) @ np.asarray(w["pos"])],
+                                        quat=[float(x) for x in quat_mul(o_q, [0.0, 0.0, np.sin(w["yaw"] / 2), np.cos(w["yaw"] / 2)])], half=w["half"])
+                                   for w in walls]
+                warnings.warn(f"gym.load_asset: {key}: the collision mesh of the single body is a ring: simulated as {ring_k} static wall boxes "
+                              f"(MI_SHIM_RING_WALLS), worst gap between the ring and the boxes {gap * 1e3:.1f} mm")
+            elif box["hollow"]:
                 warnings.warn(f"gym.load_asset: {key}: the collision mesh of the single body is a ring (its bounding box would swallow what stands inside): "
                               f"the body is created WITHOUT a collision shape")
             elif box["mesh"]:
@@ -517,6 +561,7 @@ class _Sim:
         self.attractors = []                   # create_rigid_body_attractor, env 0
         self.walked = False                    # a per-env property call has reached an env other than the newest: creation is over
         self.scene = None                      # prepare_sim: slot -> ("free" | "static", index) of the box actors the engine simulates beside a fixed-base actor
+        self.scene_statics = []                # prepare_sim: every static box of the scene, dicts pos / quat / half / mu (index = the j of ("static", j))
         self.props = None                      # _ActorProps: what the per-env property setters wrote (domain randomisation), staged on the host
 
     # the articulated actor (the engine's robot) and the free objects
@@ -1120,6 +1165,13 @@ class Gym:
                 tp.drive_vmax[d] = vm if 0.0 < vm < 1e6 else 0.0
             boxes = [(k, sl) for k, sl in enumerate(sim.slots) if sl["asset"].spec is None]
             sim.scene = None
+            # the scene's static boxes in full, dicts pos / quat / half / mu (the form oracle/scene.py takes).  Up to MI_SCENE_MAX_STATIC of them are
+            # MiScene.static_* and nothing else happens; 5 to MI_SCENE_MAX_STATIC_WIDE ask for the robot's wide-capacity library and go through
+            # mi_engine_set_scene_statics after create (tp.scene keeps the first four).  MI_SHIM_STATIC_CAPACITY=12 forces that path for any scene.
+            sim.scene_statics = []
+            static_cap, ring_walls = native.MI_SCENE_MAX_STATIC, False
+            if int(os.environ.get("MI_SHIM_STATIC_CAPACITY", "0") or 0) == native.MI_SCENE_MAX_STATIC_WIDE:
+                static_cap = native.MI_SCENE_MAX_STATIC_WIDE
             if boxes and spec.fixed_base:
                 # the other actors of the env (franka_cube_stack.py:212-233,330-339: gym.create_box assets): the engine's scene of free and
                 # static boxes beside the fixed-base actor (include/mi_engine.h MiScene, csrc/core/scene_engine.hpp)
@@ -1135,7 +1187,7 @@ class Gym:
                     if a.object_type != "box" and bool(getattr(a.options, "fix_base_link", False)):
                         raise NotImplementedError(f"the static bodies of a scene are boxes (got a {a.object_type} with fix_base_link): spheres and capsules are free bodies")
                     g_r, g_k = rslot.get("group", -1), sl.get("group", -1)
-                    if getattr(a, "hollow", False):
+                    if getattr(a, "hollow", False) and getattr(a, "ring_boxes", None) is None:
                         continue       # a ring wall without a collision shape (load_asset warned): lives in the stand-in
                     if g_r != -1 and g_k != -1 and g_r != g_k:
                         continue       # another collision group than the robot's in its own env (trifinger.py:561-563: the goal marker): touches nothing, lives in the stand-in
@@ -1152,17 +1204,39 @@ class Gym:
                         raise NotImplementedError("a static box of the scene stands at the same env-local pose in every env")
                     shape, half, m, ine = _scene_body(a)
                     mu = float(sl["friction"].get(0, 1.0)) if sl["friction"] else 1.0
+                    if getattr(a, "ring_boxes", None) is not None:
+                        # a ring wall as K static boxes (MI_SHIM_RING_WALLS): ONE actor with one rigid body, as ever; its boxes ride on its pose
+                        if not fixed or (g_r != -1 and g_k != -1 and g_r != g_k):
+                            raise NotImplementedError("a ring wall is a fixed body (fix_base_link) in the robot's collision group")
+                        ps0 = np.asarray(sl["poses"], float)
+                        if np.abs(ps0 - ps0[0]).max() > 1e-9:
+                            raise NotImplementedError("a static box of the scene stands at the same env-local pose in every env")
+                        first = len(sim.scene_statics)
+                        if first + len(a.ring_boxes) > native.MI_SCENE_MAX_STATIC_WIDE:
+                            raise NotImplementedError(f"a scene holds at most {native.MI_SCENE_MAX_STATIC_WIDE} static boxes")
+                        mu_w = float(sl["friction"].get(0, 1.0)) if sl["friction"] else 1.0
+                        for w in a.ring_boxes:
+                            sim.scene_statics.append(dict(pos=[float(x) for x in ps0[0, 0:3] + quat_to_mat(ps0[0, 3:7]) @ np.asarray(w["pos"])],
+                                                          quat=[float(x) for x in quat_mul(ps0[0, 3:7], w["quat"])], half=list(w["half"]), mu=mu_w))
+                        sim.scene[k] = ("walls", first, len(a.ring_boxes))
+                        ring_walls = True
+                        continue
                     if fixed:
-                        j = sc.n_static
-                        if j >= native.MI_SCENE_MAX_STATIC:
-                            raise NotImplementedError(f"a scene holds at most {native.MI_SCENE_MAX_STATIC} static boxes")
-                        for c in range(3):
-                            sc.static_pos[j][c], sc.static_half[j][c] = float(ps[0, c]), float(half[c])
-                        for c in range(4):
-                            sc.static_quat[j][c] = float(ps[0, 3 + c])
-                        sc.static_mu[j] = mu
+                        j = len(sim.scene_statics)
+                        if j >= native.MI_SCENE_MAX_STATIC_WIDE:
+                            raise NotImplementedError(f"a scene holds at most {native.MI_SCENE_MAX_STATIC_WIDE} static boxes")
+                        sim.scene_statics.append(dict(pos=[float(x) for x in ps[0, 0:3]], quat=[float(x) for x in ps[0, 3:7]],
+                                                      half=[float(x) for x in half], mu=mu))
                         sim.scene[k] = ("static", j)
-                        sc.n_static = j + 1
+                        if j < native.MI_SCENE_MAX_STATIC:
+                            for c in range(3):
+                                sc.static_pos[j][c], sc.static_half[j][c] = float(ps[0, c]), float(half[c])
+                            for c in range(4):
+                                sc.static_quat[j][c] = float(ps[0, 3 + c])
+                            sc.static_mu[j] = mu
+                            sc.n_static = j + 1
+                        else:
+                            static_cap = native.MI_SCENE_MAX_STATIC_WIDE
                     else:
                         j = sc.n_free
                         if j >= native.MI_SCENE_MAX_FREE:
@@ -1178,7 +1252,20 @@ class Gym:
             elif getattr(asset.options, "disable_gravity", False):      # franka_cube_stack.py:186: the only articulated actor of the env does not feel gravity
                 for i in range(3):
                     p.gravity[i] = 0.0
-            lib_path = runtime.variant_library(asset.model_name, sp, sim.device, sensors=sens)
+            if ring_walls:
+                # the statics in their order of creation, walls included: MiScene's four are the first four of the full list, and more than
+                # four -- or any wall behind the fourth place -- go through the wide library
+                for j, s_ in enumerate(sim.scene_statics[:native.MI_SCENE_MAX_STATIC]):
+                    for c in range(3):
+                        sc.static_pos[j][c], sc.static_half[j][c] = s_["pos"][c], s_["half"][c]
+                    for c in range(4):
+                        sc.static_quat[j][c] = s_["quat"][c]
+                    sc.static_mu[j] = s_["mu"]
+                sc.n_static = min(len(sim.scene_statics), native.MI_SCENE_MAX_STATIC)
+                if len(sim.scene_statics) > native.MI_SCENE_MAX_STATIC:
+                    static_cap = native.MI_SCENE_MAX_STATIC_WIDE
+            wide = sim.scene is not None and static_cap != native.MI_SCENE_MAX_STATIC
+            lib_path = runtime.variant_library(asset.model_name, sp, sim.device, sensors=sens, **(dict(static_capacity=static_cap) if wide else {}))
             asset.engine_spec = sp
         elif asset.task == "Cartpole":
             from ...tasks.cartpole import cartpole_params_from_cfg
@@ -1283,6 +1370,8 @@ class Gym:
             from ...assets import runtime
             lib_path = runtime.variant_library(asset.model_name, asset.spec, sim.device, sensors=own_sensors)
         sim.engine = native.Engine(asset.task, p, tp, n, sim.device, terrain=terrain, lib_path=lib_path)
+        if asset.generic and sim.scene is not None and static_cap != native.MI_SCENE_MAX_STATIC:
+            sim.engine.set_scene_statics(sim.scene_statics)       # the full set, the first four included
         if sim.device != "cpu":
             native.select_multi_wave(sim.engine, asset.task, n)        # the launch shape (and with it the solver order) make() would pick
         if asset.has_self_collision:
@@ -1304,7 +1393,8 @@ class Gym:
                 mu[e] = val
             t["friction"][:] = mu.to(sim.device)
         if getattr(sim, "scene", None):
-            for k, (kind, j) in sim.scene.items():
+            for k, ent in sim.scene.items():
+                kind, j = ent[0], ent[1]
                 if kind == "free":
                     o = torch.zeros((n, 13), dtype=torch.float32)
                     o[:, :7] = torch.tensor(sim.slots[k]["poses"], dtype=torch.float32)

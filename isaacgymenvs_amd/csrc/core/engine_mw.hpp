@@ -119,13 +119,18 @@ struct SimMW : Sim<M> {
     // loads issued by the caller), 2: already IN the row store, left there by the previous sub-step of the same launch (KEEP).
     // KEEP: leave the signed limit impulses in the row store for a following sub-step of the same launch (mw_kernels.hpp, fused sub-steps);
     // the contact impulses are there anyway.
+    // outputs(), asked in P5 (the same answer for every role and lane of the launch): false = a sub-step whose lamc / laml / dof_force / sensor / netf a
+    // following sub-step of the same launch overwrites before anything can read them (mw_kernels.hpp, every fused sub-step but the last): P5 skips the
+    // stores and the sensor arithmetic behind them.  What the next sub-step reads -- the signed limit impulses in the row store (KEEP), q / qd / root --
+    // is left as ever.  (A callable, not a bool: a flag formed before P1 would sit in a register pair through the whole sub-step.)
     // SENS: also leave the force-sensor values of the own bodies (the very floats stored to `sensor`) in sens_own, for a post step that runs
     // on the same wave (mw_kernels.hpp loco_post_role) and would otherwise read them straight back from memory.
     float sens_own[6 * M::NSENSA];      // written with SENS only; entries of other roles' sensors are never set
-    template <int R, bool KEEP = false, bool SENS = false, int RS, class GND, class BAR>
+    struct AllOutputs { MI_HD constexpr bool operator()() const { return true; } };
+    template <int R, bool KEEP = false, bool SENS = false, int RS, class GND, class BAR, class OUT = AllOutputs>
     MI_HD void substep_role(const SimParams& P, const float* tau, const float h, const RowStore<RS> rows, const Strided lamc,
                             const Strided laml, const Strided sensor, const Strided dof_force, const GND& gnd, const float mu_env,
-                            const Strided netf, const int stage, const BAR& bar) {
+                            const Strided netf, const int stage, const BAR& bar, const OUT& outputs = OUT{}) {
         static_assert(!M::FIXED, "multi-wave sub-step: free-base models");
         auto G = [&](int row, int cc) MI_LAMBDA -> float& { return rows(row * M::MAXCHAIN + cc); };
         auto Ainv = [&](int row) MI_LAMBDA -> float& { return rows(NROWG * M::MAXCHAIN + row); };
@@ -530,6 +535,7 @@ struct SimMW : Sim<M> {
             }
         });
         MI_PHASE();
+        const bool out = outputs();
         sfor<ND>([&](auto D) MI_LAMBDA {
             constexpr int d = D;
             if constexpr (owns_gi<R>(OFF + d)) {
@@ -540,58 +546,62 @@ struct SimMW : Sim<M> {
                     ll = (dl < du) ? lam(row) : -lam(row);
                     if constexpr (KEEP) lam(row) = ll;
                 }
-                laml(d) = ll;
-                dof_force(d) = tau[d] - M::dof_stiffness[d] * sc_stiff[d] * (q[d] - M::dof_springref[d]) - M::dof_damping[d] * sc_damp[d] * v[OFF + d] + ll * invh;
-            }
-        });
-        float sens[6 * M::NSENSA];
-        sfor<6 * NSENS>([&](auto K) MI_LAMBDA { sens[K] = 0.f; });
-        float nf[GND::NETF ? NB : 1][3];
-        if constexpr (GND::NETF) sfor<NB>([&](auto B_) MI_LAMBDA { nf[B_][0] = nf[B_][1] = nf[B_][2] = 0.f; });
-        sfor<NSPH>([&](auto S_) MI_LAMBDA {
-            constexpr int s = S_, b = M::sph_body[s], row0 = NLIM + 3 * s;
-            if constexpr (owns_body<R>(b)) {
-                if (!(sph_active >> s & 1ull)) {
-                    lamc(3 * s) = 0.f; lamc(3 * s + 1) = 0.f; lamc(3 * s + 2) = 0.f;
-                    return;
-                }
-                const float ln = lam(row0), l1 = lam(row0 + 1), l2 = lam(row0 + 2);
-                lamc(3 * s) = ln; lamc(3 * s + 1) = l1; lamc(3 * s + 2) = l2;
-                float f[3], xc[3];
-                if constexpr (GND::HEIGHTFIELD) {
-                    float n[3], t1[3], t2[3];
-                    n[0] = vt(row0 + 1); n[1] = vt(row0 + 2);
-                    n[2] = MI_SQRT(fmaxf(1.f - n[0] * n[0] - n[1] * n[1], 0.f));
-                    contact_frame(n, t1, t2);
-                    sfor<3>([&](auto K) MI_LAMBDA {
-                        f[K] = (n[K] * ln + t1[K] * l1 + t2[K] * l2) * invh;
-                        xc[K] = c.xcs[s][K] - M::sph_rad[s] * n[K];
-                        nf[b][K] += f[K];
-                    });
-                } else {
-                    f[0] = l1 * invh; f[1] = l2 * invh; f[2] = ln * invh;
-                    xc[0] = c.xcs[s][0]; xc[1] = c.xcs[s][1]; xc[2] = c.xcs[s][2] - M::sph_rad[s];
-                    if constexpr (GND::NETF) sfor<3>([&](auto K) MI_LAMBDA { nf[b][K] += f[K]; });
-                }
-                if constexpr (B::sensor_of(b) >= 0) {
-                    constexpr int k = B::sensor_of(b);
-                    const float arm[3] = {xc[0] - c.rs[k][0], xc[1] - c.rs[k][1], xc[2] - c.rs[k][2]};
-                    float tq[3], fl[3], tl[3];
-                    cross3(arm, f, tq);
-                    matTvec3(c.Rs[k], f, fl); matTvec3(c.Rs[k], tq, tl);
-                    sfor<3>([&](auto C) MI_LAMBDA { sens[6 * k + C] += fl[C]; sens[6 * k + 3 + C] += tl[C]; });
+                if (out) {
+                    laml(d) = ll;
+                    dof_force(d) = tau[d] - M::dof_stiffness[d] * sc_stiff[d] * (q[d] - M::dof_springref[d]) - M::dof_damping[d] * sc_damp[d] * v[OFF + d] + ll * invh;
                 }
             }
         });
-        if constexpr (GND::NETF) sfor<NB>([&](auto B_) MI_LAMBDA {
-            if constexpr (owns_body<R>(B_)) sfor<3>([&](auto K) MI_LAMBDA { netf(3 * B_ + K) = nf[B_][K]; });
-        });
-        sfor<NSENS>([&](auto K_) MI_LAMBDA {
-            if constexpr (owns_body<R>(M::sens_body[K_])) sfor<6>([&](auto C) MI_LAMBDA {
-                sensor(6 * K_ + C) = sens[6 * K_ + C];
-                if constexpr (SENS) sens_own[6 * K_ + C] = sens[6 * K_ + C];
+        if (out) {
+            float sens[6 * M::NSENSA];
+            sfor<6 * NSENS>([&](auto K) MI_LAMBDA { sens[K] = 0.f; });
+            float nf[GND::NETF ? NB : 1][3];
+            if constexpr (GND::NETF) sfor<NB>([&](auto B_) MI_LAMBDA { nf[B_][0] = nf[B_][1] = nf[B_][2] = 0.f; });
+            sfor<NSPH>([&](auto S_) MI_LAMBDA {
+                constexpr int s = S_, b = M::sph_body[s], row0 = NLIM + 3 * s;
+                if constexpr (owns_body<R>(b)) {
+                    if (!(sph_active >> s & 1ull)) {
+                        lamc(3 * s) = 0.f; lamc(3 * s + 1) = 0.f; lamc(3 * s + 2) = 0.f;
+                        return;
+                    }
+                    const float ln = lam(row0), l1 = lam(row0 + 1), l2 = lam(row0 + 2);
+                    lamc(3 * s) = ln; lamc(3 * s + 1) = l1; lamc(3 * s + 2) = l2;
+                    float f[3], xc[3];
+                    if constexpr (GND::HEIGHTFIELD) {
+                        float n[3], t1[3], t2[3];
+                        n[0] = vt(row0 + 1); n[1] = vt(row0 + 2);
+                        n[2] = MI_SQRT(fmaxf(1.f - n[0] * n[0] - n[1] * n[1], 0.f));
+                        contact_frame(n, t1, t2);
+                        sfor<3>([&](auto K) MI_LAMBDA {
+                            f[K] = (n[K] * ln + t1[K] * l1 + t2[K] * l2) * invh;
+                            xc[K] = c.xcs[s][K] - M::sph_rad[s] * n[K];
+                            nf[b][K] += f[K];
+                        });
+                    } else {
+                        f[0] = l1 * invh; f[1] = l2 * invh; f[2] = ln * invh;
+                        xc[0] = c.xcs[s][0]; xc[1] = c.xcs[s][1]; xc[2] = c.xcs[s][2] - M::sph_rad[s];
+                        if constexpr (GND::NETF) sfor<3>([&](auto K) MI_LAMBDA { nf[b][K] += f[K]; });
+                    }
+                    if constexpr (B::sensor_of(b) >= 0) {
+                        constexpr int k = B::sensor_of(b);
+                        const float arm[3] = {xc[0] - c.rs[k][0], xc[1] - c.rs[k][1], xc[2] - c.rs[k][2]};
+                        float tq[3], fl[3], tl[3];
+                        cross3(arm, f, tq);
+                        matTvec3(c.Rs[k], f, fl); matTvec3(c.Rs[k], tq, tl);
+                        sfor<3>([&](auto C) MI_LAMBDA { sens[6 * k + C] += fl[C]; sens[6 * k + 3 + C] += tl[C]; });
+                    }
+                }
             });
-        });
+            if constexpr (GND::NETF) sfor<NB>([&](auto B_) MI_LAMBDA {
+                if constexpr (owns_body<R>(B_)) sfor<3>([&](auto K) MI_LAMBDA { netf(3 * B_ + K) = nf[B_][K]; });
+            });
+            sfor<NSENS>([&](auto K_) MI_LAMBDA {
+                if constexpr (owns_body<R>(M::sens_body[K_])) sfor<6>([&](auto C) MI_LAMBDA {
+                    sensor(6 * K_ + C) = sens[6 * K_ + C];
+                    if constexpr (SENS) sens_own[6 * K_ + C] = sens[6 * K_ + C];
+                });
+            });
+        }
         MI_PHASE();
         sfor<ND>([&](auto D) MI_LAMBDA {
             if constexpr (owns_gi<R>(OFF + D)) { qd[D] = v[OFF + D]; q[D] += h * qd[D]; }

@@ -155,7 +155,9 @@ struct MwFusedPostArgs {
 };
 // Kernel arguments read through the kernarg segment pointer are fetched where they are first used, one scalar-cache line at a time, and every launch
 // gets a fresh argument buffer: the first touch of a line is a miss, paid on the spot.  The part of the arguments that only the post step reads
-// would be missed behind the last sub-step, on the critical wave.  KernargLines issues one scalar load per 64-byte line of bytes [BEGIN, END) of
+// would be missed behind the last sub-step, on the critical wave; the View's pointers, SimParams, ActParams and the sub-step counts would be missed
+// one after another at the head of the role, ahead of the state loads (five or six round trips in series before the tree pass can start).  The
+// one-launch kernels therefore touch ALL their argument lines at entry.  KernargLines issues one scalar load per 64-byte line of bytes [BEGIN, END) of
 // the argument struct (and of its last dword, should the buffer not be line aligned) where it is constructed -- at kernel entry, next to the load of
 // N, so that the misses overlap -- and drop() gives the loaded words up at the wait that load has anyway: no SGPR stays live behind it.
 template <size_t BEGIN, size_t END>
@@ -170,14 +172,58 @@ struct KernargLines {
     }
     __device__ __forceinline__ void drop() const { sfor<NL>([&](auto K) MI_LAMBDA { asm volatile("" ::"s"(x[K])); }); }
 };
+// Job statistics of a role wave whose first E <= 32 lanes hold envs (the upper lanes, and the lanes of a partly filled last workgroup from the first
+// env past the batch on, have retired): the sum over the live lanes, valid in lane 0.  DPP row shifts towards lane 0 -- lane i adds lane i + 8, 4, 2, 1
+// of its row of 16 -- with bound_ctrl, which reads 0 where the source lane is past the row or has retired; the live lanes are lanes 0 .. k, so no
+// retired lane ever holds a partial sum that a live one needs.  (No LDS traffic and no live-mask arithmetic, unlike wave_sum_live: step_kernels.hpp.)
+template <int ACTIVE>
+__device__ __forceinline__ float row_sum_live(float v) {
+    static_assert(ACTIVE <= 32, "one or two DPP rows");
+#if defined(__HIP_DEVICE_COMPILE__)
+    auto shl = [](const float x, auto Nn) MI_LAMBDA {
+        constexpr int ctrl = 0x100 + decltype(Nn)::value;      // row_shl:n
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, 0xf, 0xf, true));
+    };
+    v += shl(v, std::integral_constant<int, 8>{});
+    v += shl(v, std::integral_constant<int, 4>{});
+    v += shl(v, std::integral_constant<int, 2>{});
+    v += shl(v, std::integral_constant<int, 1>{});
+    if constexpr (ACTIVE > 16) {         // the second row's sum is in lane 16, which is live if any lane of that row is
+        const unsigned long long live = __builtin_amdgcn_ballot_w64(true);
+        const float upper = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+        v += ((live >> 16) & 1ull) ? upper : 0.f;
+    }
+#endif
+    return v;
+}
+// episode_stats (step_kernels.hpp) for the one-launch kernel: the same four sums of the workgroup's live envs, from lane 0 with row_sum_live; the
+// count of live envs -- which over the launch always adds up to N -- is added once, as N, by the lane that holds env 0.
+template <int E>
+__device__ __forceinline__ void episode_stats_row(const View& v, const int e, const float rew, const long long reset, const long long progress, const float ep_ret) {
+    float ret = ep_ret + rew, fin_ret = 0.f, fin_len = 0.f, fin = 0.f;
+    if (reset != 0) { fin_ret = ret; fin_len = (float)(progress + 1); fin = 1.f; ret = 0.f; }
+    v.ep_ret[e] = ret;
+    fin_ret = row_sum_live<E>(fin_ret); fin_len = row_sum_live<E>(fin_len); fin = row_sum_live<E>(fin);
+    const float r = row_sum_live<E>(rew);
+    if ((threadIdx.x & 63) == 0) {
+        if (fin > 0.f) { stat_add(v.stats + 0, fin_ret); stat_add(v.stats + 1, fin_len); stat_add(v.stats + 2, fin); }
+        stat_add(v.stats + 3, r);
+        if (e == 0) stat_add(v.stats + 4, (float)v.N);
+    }
+}
 // S: the role's simulator (SimMW<M>; SimMWC<M> for the Humanoid, whose launch is its LAST sub-step's: mwc_kernels.hpp).  act: the clamped actions in
 // the role's registers, or nullptr -- then they are read back from v.actions (stored by the step's first launch).  BAR_FIRST: a barrier before
 // anything is written to xpost (an area some role may still be reading in its output phase).  SENS_REG: the force-sensor values of the own bodies
 // are in sim.sens_own (left there by the last sub-step's P5, substep_role<R, KEEP, SENS>); otherwise they are read back from v.sensor.
-template <class S, class M, bool HUM, int E, int R, bool BAR_FIRST = false, bool SENS_REG = false>
+// SPLIT: the job statistics leave the trunk role, the one wave the workgroup is still waiting for behind the last barrier.  Before that barrier the
+// trunk role publishes the eight words the reward needs besides the dof sums (o12[0], o12[10], o12[11], potentials, prev_potentials, progress in two
+// words, the running return) behind the reward terms in xpost; behind it the leg role STAT_ROLE forms the same sums and the same reward with the
+// same code, stores the running return and adds the statistics (episode_stats_row), while the trunk role stores the reward and the flags.
+template <class S, class M, bool HUM, int E, int R, bool BAR_FIRST = false, bool SENS_REG = false, bool SPLIT = false>
 __device__ __forceinline__ void loco_post_role(const View& v, const LocoParams& tp, S& sim, const float* act, const int e, float* xpost) {
     using T = Loco<M::ND, 6 * M::NSENS, HUM>;
     constexpr int ND = M::ND, NOBS = T::NOBS;
+    constexpr int STAT_ROLE = (M::TRUNK_ROLE + 1) % M::NROLE, XS = 3 * ND;      // (XS: first of the eight published words)
     const int N = v.N;
     if constexpr (BAR_FIRST) __syncthreads();
     const uint32_t genv = (uint32_t)(v.env_offset + e);
@@ -228,7 +274,33 @@ __device__ __forceinline__ void loco_post_role(const View& v, const LocoParams& 
         }
     });
     if (do_reset) sfor<3 * M::NSPH>([&](auto K) MI_LAMBDA { if constexpr (S::template owns_body<R>(M::sph_body[K / 3])) v.lamc[K * N + e] = 0.f; });
-    if constexpr (R != M::TRUNK_ROLE) { __syncthreads(); return; }
+    // the reward from the roles' terms in xpost (behind the barrier) and the trunk role's scalars: loco_post_env's partial sums, part[d & 3]
+    auto reward_of = [&](const float o0, const float o10, const float o11, const long long prog, const float pot, const float prev_pot, float* rew,
+                         long long* reset) MI_LAMBDA {
+        typename T::DofSums part[4];
+        sfor<ND>([&](auto D) MI_LAMBDA {
+            constexpr int d = D;
+            part[d & 3].actions += xpost[(3 * d + 0) * E]; part[d & 3].electricity += xpost[(3 * d + 1) * E]; part[d & 3].at_limit += xpost[(3 * d + 2) * E];
+        });
+        typename T::DofSums sm;
+        sm.actions = (part[0].actions + part[1].actions) + (part[2].actions + part[3].actions);
+        sm.electricity = (part[0].electricity + part[1].electricity) + (part[2].electricity + part[3].electricity);
+        sm.at_limit = (part[0].at_limit + part[1].at_limit) + (part[2].at_limit + part[3].at_limit);
+        T::reward_total(tp, o0, o10, o11, sm, 0LL, prog, pot, prev_pot, rew, reset);
+    };
+    if constexpr (R != M::TRUNK_ROLE) {
+        __syncthreads();
+        if constexpr (SPLIT && R == STAT_ROLE) {
+            float pub[8];
+            sfor<8>([&](auto K) MI_LAMBDA { pub[K] = xpost[(XS + K) * E]; });
+            const long long prog = (long long)(((unsigned long long)__float_as_uint(pub[6]) << 32) | (unsigned long long)__float_as_uint(pub[5]));
+            float rew;
+            long long reset;
+            reward_of(pub[0], pub[1], pub[2], prog, pub[3], pub[4], &rew, &reset);
+            episode_stats_row<E>(v, e, rew, reset, prog, pub[7]);
+        }
+        return;
+    }
     // ---- trunk role: root part, reward, flags
     float prev_potentials;
     if (do_reset) {
@@ -244,20 +316,18 @@ __device__ __forceinline__ void loco_post_role(const View& v, const LocoParams& 
     float up_vec[3], heading_vec[3], o12[12];
     T::obs_root(tp, sim.root, tp.targets, potentials, tp.inv_start_rot, tp.basis_vec0, tp.basis_vec1, o12, &potentials, &prev_potentials, up_vec, heading_vec);
     sfor<12>([&](auto K) MI_LAMBDA { put(K, o12[K]); });
+    if constexpr (SPLIT) {
+        xpost[(XS + 0) * E] = o12[0]; xpost[(XS + 1) * E] = o12[10]; xpost[(XS + 2) * E] = o12[11];
+        xpost[(XS + 3) * E] = potentials; xpost[(XS + 4) * E] = prev_potentials;
+        xpost[(XS + 5) * E] = __uint_as_float((uint32_t)((unsigned long long)progress & 0xffffffffull));
+        xpost[(XS + 6) * E] = __uint_as_float((uint32_t)((unsigned long long)progress >> 32));
+        xpost[(XS + 7) * E] = ep_ret;
+    }
     __syncthreads();
-    typename T::DofSums part[4];
-    sfor<ND>([&](auto D) MI_LAMBDA {
-        constexpr int d = D;
-        part[d & 3].actions += xpost[(3 * d + 0) * E]; part[d & 3].electricity += xpost[(3 * d + 1) * E]; part[d & 3].at_limit += xpost[(3 * d + 2) * E];
-    });
-    typename T::DofSums sm;
-    sm.actions = (part[0].actions + part[1].actions) + (part[2].actions + part[3].actions);
-    sm.electricity = (part[0].electricity + part[1].electricity) + (part[2].electricity + part[3].electricity);
-    sm.at_limit = (part[0].at_limit + part[1].at_limit) + (part[2].at_limit + part[3].at_limit);
     float rew;
     long long reset;
-    T::reward_total(tp, o12[0], o12[10], o12[11], sm, 0LL, progress, potentials, prev_potentials, &rew, &reset);
-    episode_stats<E, true>(v, e, true, rew, reset, progress, ep_ret);
+    reward_of(o12[0], o12[10], o12[11], progress, potentials, prev_potentials, &rew, &reset);
+    if constexpr (!SPLIT) episode_stats<E, true>(v, e, true, rew, reset, progress, ep_ret);
     v.randomize[e] = randomize + 1;
     v.episode[e] = ep;
     v.potentials[e] = potentials;
@@ -284,6 +354,20 @@ __device__ __forceinline__ void mw_role_fused(const MwFusedArgs<GND>& a, float* 
 #endif
     load_sim(sim, v, e);
     load_actor_scales(sim, v, e);
+    // what sub-step 0 derives its efforts from -- the caller's actions, the stored ones, or the stored efforts -- and the env's friction: loaded here, in
+    // one group with the state above and ahead of the LDS-direct loads, so that P1 waits for one round trip of memory (the kernel's arguments are
+    // all in the scalar cache by now: KernargLines at kernel entry)
+    float tau[M::NDA], act[M::NDA];
+    sfor<ND>([&](auto K) MI_LAMBDA { tau[K] = 0.f; act[K] = 0.f; });
+    const int src0 = (0 >= a.n_sub - a.tail) ? (int)ACT_STORED_TAU : a.first;
+    if (src0 == ACT_FROM_ACTIONS) {
+        sfor<ND>([&](auto K) MI_LAMBDA { if (K < ap.nact) act[K] = a.actions_in[(size_t)e * ap.nact + K]; });       // (not yet clamped)
+    } else if (src0 > 0) {
+        sfor<ND>([&](auto K) MI_LAMBDA { if (K < ap.nact) act[K] = v.actions[K * N + e]; });
+    } else {
+        sfor<ND>([&](auto K) MI_LAMBDA { tau[K] = v.tau[K * N + e]; });
+    }
+    const float mu_env = (GND::HEIGHTFIELD || v.friction != nullptr) ? v.friction[e] : -1.f;
     {   // last step's impulses of the own rows: HBM -> row-store slots, LDS-direct (as in mw_role)
         typedef const __attribute__((address_space(1))) void* gptr_t;
         typedef __attribute__((address_space(3))) void* lptr_t;
@@ -305,15 +389,10 @@ __device__ __forceinline__ void mw_role_fused(const MwFusedArgs<GND>& a, float* 
     const float h = a.P.dt / (float)a.P.substeps;
     const Strided lamc{v.lamc + e, N}, laml{v.laml + e, N}, sensor{v.sensor + e, N}, dof_force{v.dof_force + e, N};
     const Strided netf{GND::NETF ? v.netf + e : nullptr, N};
-    const float mu_env = (GND::HEIGHTFIELD || v.friction != nullptr) ? v.friction[e] : -1.f;
     float* xroot = lds_rows + (size_t)S::MW_SLOTS * E + lane;     // [13][E] the new root state, trunk role -> the others
-    float tau[M::NDA], act[M::NDA];
-    sfor<ND>([&](auto K) MI_LAMBDA { tau[K] = 0.f; act[K] = 0.f; });
     for (int i = 0; i < a.n_sub; ++i) {
         const int src = (i >= a.n_sub - a.tail) ? (i == 0 ? (int)ACT_STORED_TAU : -1) : (i == 0 ? a.first : a.rest);   // -1: keep the efforts
-        if (src == ACT_STORED_TAU) {
-            if (i == 0) sfor<ND>([&](auto K) MI_LAMBDA { tau[K] = v.tau[K * N + e]; });
-        } else if (src > 0) {
+        if (src > 0) {      // (ACT_STORED_TAU: sub-step 0 has them from the head, a later one keeps them)
             // (only the efforts of the dofs this role sees matter to it; it stores the ones it owns)
             sfor<ND>([&](auto K) MI_LAMBDA {
                 constexpr int k = K;
@@ -322,15 +401,12 @@ __device__ __forceinline__ void mw_role_fused(const MwFusedArgs<GND>& a, float* 
                 if (k < ap.nact) {
                     float x;
                     if (src == ACT_FROM_ACTIONS) {
-                        x = a.actions_in[(size_t)e * ap.nact + k];
-                        x = fminf(fmaxf(x, -ap.clip), ap.clip);
+                        if (i != 0) act[k] = a.actions_in[(size_t)e * ap.nact + k];      // (sub-step 0: loaded at the head, not yet clamped)
+                        x = fminf(fmaxf(act[k], -ap.clip), ap.clip);
                         if constexpr (mine) v.actions[k * N + e] = x;
                         act[k] = x;
-                    } else if (i == 0) {
-                        x = v.actions[k * N + e];
-                        act[k] = x;
                     } else {
-                        x = act[k];
+                        x = act[k];      // (the stored actions: loaded at the head)
                     }
                     if (ap.mode == 0) {
                         t = x * ap.gear[k] * ap.scale;
@@ -351,7 +427,7 @@ __device__ __forceinline__ void mw_role_fused(const MwFusedArgs<GND>& a, float* 
         sim.tstamp = (tstamp != nullptr && i < 3) ? tstamp + 8 * i : nullptr;
 #endif
         sim.template substep_role<R, true, POST>(a.P, tau, h, RowStore<E>{lds_rows + lane}, lamc, laml, sensor, dof_force, a.gnd, mu_env, netf,
-                                           i == 0 ? 1 : 2, DevBarrier{});
+                                           i == 0 ? 1 : 2, DevBarrier{}, [&]() MI_LAMBDA { return i + 1 == a.n_sub; });     // (outputs: the next sub-step would overwrite them unread)
         if constexpr (GND::HEIGHTFIELD) {
             if (i == a.n_sub - a.tail - 1 && v.dof_api != nullptr)       // (uniform) the task's refresh_dof_state_tensor at the end of its decimation loop
                 sfor<ND>([&](auto K) MI_LAMBDA {
@@ -380,8 +456,8 @@ __device__ __forceinline__ void mw_role_fused(const MwFusedArgs<GND>& a, float* 
         }
     }
     if constexpr (POST) {
-        static_assert(3 * M::ND <= 16 * S::NLR, "the reward terms fit the (by now dead) tree-pass exchange area");
-        loco_post_role<S, M, HUM, E, R, false, true>(v, *tp, sim, act, e, lds_rows + (size_t)S::X_LR * E + lane);
+        static_assert(3 * M::ND + 8 <= 16 * S::NLR, "the reward terms and the trunk role's eight words fit the (by now dead) tree-pass exchange area");
+        loco_post_role<S, M, HUM, E, R, false, true, true>(v, *tp, sim, act, e, lds_rows + (size_t)S::X_LR * E + lane);
         MI_STAMP(31);
         return;
     }
@@ -404,13 +480,11 @@ __global__ __launch_bounds__(64 * M::NROLE, E == 8 ? 2 : 1) void substep_mw_fuse
     const MwFusedPostArgs<GND>& a = *reinterpret_cast<const MwFusedPostArgs<GND>*>(__builtin_amdgcn_kernarg_segment_ptr());
     const int lane = threadIdx.x;
     if (lane >= E) return;
-    // what only the post step reads: the View's pointers from `potentials` to `stats`, and the task parameters
-    const KernargLines<offsetof(MwFusedPostArgs<GND>, f.v.potentials), offsetof(MwFusedPostArgs<GND>, f.v.stats) + sizeof(float*)> view_tail(&a);
-    const KernargLines<offsetof(MwFusedPostArgs<GND>, tp), sizeof(MwFusedPostArgs<GND>)> task_params(&a);
+    // every line of the arguments, what the post step reads behind the last sub-step as well as what the head of the role reads a few instructions on
+    const KernargLines<0, sizeof(MwFusedPostArgs<GND>)> all_args(&a);
     const int N = a.f.v.N;
     asm volatile("" ::"s"(N));           // (N loaded in the same group, waited for together)
-    view_tail.drop();
-    task_params.drop();
+    all_args.drop();
     const int e = xcd_env_base<E>(blockIdx.x) + lane;
     if (e >= N) return;
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.y);
@@ -431,8 +505,12 @@ __global__ __launch_bounds__(64 * M::NROLE) void substep_mw_fused_kernel(MwFused
     const MwFusedArgs<GND>& a = *reinterpret_cast<const MwFusedArgs<GND>*>(__builtin_amdgcn_kernarg_segment_ptr());
     const int lane = threadIdx.x;
     if (lane >= E) return;
+    const KernargLines<0, sizeof(MwFusedArgs<GND>)> all_args(&a);        // (as in substep_mw_fused_post_kernel)
+    const int N = a.v.N;
+    asm volatile("" ::"s"(N));
+    all_args.drop();
     const int e = xcd_env_base<E>(blockIdx.x) + lane;
-    if (e >= a.v.N) return;
+    if (e >= N) return;
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.y);
     switch (role) {
         case 0: mw_role_fused<M, GND, E, 0>(a, lds_rows, e, lane); break;

@@ -16,8 +16,9 @@ struct AnymalAcc {
     double cmdnorm = 0, sums[kAnymalSums] = {0}, cnt = 0, lv = 0;
     StatAcc st;
 };
-struct HostRed {
+struct HostRed : HostEpisodeRed {
     AnymalAcc* a;
+    explicit HostRed(AnymalAcc* acc) : HostEpisodeRed{&acc->st}, a(acc) {}
     void cmdnorm(const View&, float acc) const { a->cmdnorm += acc; }
     void extras(const View&, const float (&st_sums)[kAnymalSums], float st_cnt, float lv) const {
         if (st_cnt > 0.f) {
@@ -25,9 +26,6 @@ struct HostRed {
             a->cnt += st_cnt;
         }
         a->lv += lv;
-    }
-    void episode(const View& v, int e, bool valid, float rew, long long reset, long long progress) const {
-        if (valid) episode_stats_env(v, e, rew, reset, progress, a->st);
     }
 };
 

@@ -1,5 +1,5 @@
 // cpu_engine.hpp -- what the translation units of the CPU backend share: the engine object (the lifecycle core of csrc/engine_core.hpp plus what
-// only this backend has) and the per-thread statistics accumulators.
+// only this backend has), the per-thread statistics accumulators and the host's reduction policy for them.
 // (cpu/mi_engine_cpu.cpp: C ABI + Cartpole / Ant / Humanoid / Quadcopter / Ingenuity / BallBalance; cpu/cpu_anymal.cpp: AnymalTerrain, Anymal;
 //  cpu/cpu_articulation.cpp: the run-time robot; cpu/cpu_hand.cpp, compiled once per hand and object shape: ShadowHand, AllegroHand.)
 #pragma once
@@ -31,6 +31,13 @@ static inline void episode_stats_env(const View& v, int en, float rew, long long
     if (reset != 0) { a.fin_ret += ret; a.fin_len += (double)(progress + 1); a.fin += 1; ret = 0.f; }
     v.ep_ret[en] = ret;
 }
+// the job-statistics reduction policy of the per-env post bodies shared with the kernels (tasks/*_step.hpp); the host has no shadow lanes
+struct HostEpisodeRed {
+    StatAcc* st;
+    void episode(const View& v, int e, bool valid, float rew, long long reset, long long progress) const {
+        if (valid) episode_stats_env(v, e, rew, reset, progress, *st);
+    }
+};
 static inline void flush_stats(const View& v, const std::vector<StatAcc>& accs) {
     for (const StatAcc& a : accs) { v.stats[0] += (float)a.fin_ret; v.stats[1] += (float)a.fin_len; v.stats[2] += (float)a.fin; v.stats[3] += (float)a.r; v.stats[4] += (float)a.cnt; }
 }

@@ -3,8 +3,9 @@
 // What it is for: the reference's `sim_device=cpu pipeline=cpu` configuration (BASELINE.json config 1: Cartpole num_envs=64;
 // reference device resolution isaacgymenvs/tasks/base/vec_task.py:78-88, PhysX worker threads `num_threads`, cfg/config.yaml:30).
 // What it is built from: the SAME sources the HIP kernels compile -- csrc/core/engine.hpp (per-env physics sub-step, host build of
-// the specialised code), csrc/tasks/locomotion.hpp (observations / reward / reset), csrc/arena_layout.hpp (arena layout) -- with
-// OpenMP over envs where the kernels have one env per lane.  It does NOT use oracle/ (test infrastructure).  Same SoA arena layout,
+// the specialised code), csrc/tasks/locomotion.hpp (observations / reward / reset), csrc/tasks/*_step.hpp (the per-env pre / post / reset /
+// init bodies of Cartpole, Quadcopter, Ingenuity and BallBalance), csrc/arena_layout.hpp (arena layout) -- with OpenMP over envs where the
+// kernels have one env per lane.  It does NOT use oracle/ (test infrastructure).  Same SoA arena layout,
 // same counter-based reset RNG: the Python side sees identical tensors and, up to fp32 summation order in the episode statistics,
 // identical numbers on both devices.
 //
@@ -16,6 +17,9 @@
 #include "cpu_engine.hpp"
 #include "cpu_hand.hpp"
 #include "../core/bbot_engine.hpp"
+#include "../tasks/quadcopter_step.hpp"
+#include "../tasks/ingenuity_step.hpp"
+#include "../tasks/ball_balance_step.hpp"
 
 static thread_local std::string g_err;
 static int fail(const std::string& m) { g_err = m; return -1; }
@@ -96,27 +100,13 @@ extern "C" int mi_engine_init_state(MiEngine* e, void*) {
         return rc == -2 ? fail("mi_engine_init_state: the hand model of this library and its task table have different sizes (a variant built without its engine unit)") : rc;
     }
     if (e->task == T_ANYMAL && e->terrain.hs == nullptr) return fail("mi_engine_init_state: AnymalTerrain needs mi_engine_set_terrain first");
-    const float root_z = core_init_root_z(*e);
-    const float root[13] = {0, 0, root_z, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0};
     const View v0 = init_view(*e);
     for (int en = 0; en < N; ++en)
-        init_env_constants(v0, en, m.nd, 3 * m.nsph, 6 * m.nsens, m.nobs, m.nact, root_z, core_is_loco(*e) ? e->loco.initial_dof_pos : nullptr, core_init_potential(*e));
-    for (int en = 0; en < N; ++en) {      // the tasks' own tensors (quad_init_kernel / ing_init_kernel / bbot_init_kernel)
-        if (e->task == T_QUADCOPTER) {
-            for (int d = 0; d < kQuadDof; ++d) e->qv.targets[d * N + en] = 0.f;
-            for (int k = 0; k < kQuadRotors; ++k) e->qv.thrusts[k * N + en] = 0.f;
-            for (int k = 0; k < 3 * ModelQuadcopter::NB; ++k) e->qv.forces[k * N + en] = 0.f;
-        } else if (e->task == T_INGENUITY) {
-            for (int k = 0; k < 13; ++k) e->iv.marker[k * N + en] = root[k];
-            for (int k = 0; k < 3; ++k) e->iv.target[k * N + en] = (k == 2) ? 1.f : 0.f;
-            for (int k = 0; k < 3 * kIngRotors; ++k) e->iv.thrusts[k * N + en] = 0.f;
-            for (int k = 0; k < 3 * kIngBodies; ++k) e->iv.forces[k * N + en] = 0.f;
-        } else if (e->task == T_BALLBALANCE) {
-            for (int k = 0; k < 13; ++k) e->bv.ball[k * N + en] = (k < 3) ? e->bbot.ball_init_pos[k] : (k == 6 ? 1.f : 0.f);
-            for (int d = 0; d < kBbotDof; ++d) e->bv.targets[d * N + en] = 0.f;
-            for (int k = 0; k < 9; ++k) e->bv.lamp[k * N + en] = 0.f;
-            e->bv.ncontact[en] = 0;
-        }
+        init_env_constants(v0, en, m.nd, 3 * m.nsph, 6 * m.nsens, m.nobs, m.nact, core_init_root_z(*e), core_is_loco(*e) ? e->loco.initial_dof_pos : nullptr, core_init_potential(*e));
+    for (int en = 0; en < N; ++en) {      // the tasks' own tensors
+        if (e->task == T_QUADCOPTER) quad_init_env(e->v, e->qv, e->quad, en);
+        else if (e->task == T_INGENUITY) ing_init_env(e->v, e->iv, e->ing, en);
+        else if (e->task == T_BALLBALANCE) bbot_init_env(e->v, e->bv, e->bbot, en);
     }
     e->steps = 0;
     if (e->task == T_ANYMAL || e->task == T_ANYMAL_FLAT) {
@@ -200,43 +190,11 @@ static void loco_post_env(const View& v, const LocoParams& tp, int en, StatAcc& 
     if (v.obs_noise.dist != 0)
         for (int k = 0; k < NOBS; ++k) obs[k] = apply_noise(v.obs_noise, v.seed, (uint32_t)(v.env_offset + en), v.step, 0u, (uint32_t)k, obs[k]);
     episode_stats_env(v, en, rew, reset, progress, acc);
-    v.randomize[en] += 1;
     v.episode[en] = ep;
     v.potentials[en] = potentials; v.prev_potentials[en] = prev_potentials;
     for (int k = 0; k < 3; ++k) { v.up_vec[k * N + en] = up_vec[k]; v.heading_vec[k * N + en] = heading_vec[k]; }
-    float* ob = v.obs + (size_t)en * NOBS;
-    float* oc = v.obs_out + ((size_t)v.ring * N + en) * NOBS;
-    for (int k = 0; k < NOBS; ++k) { ob[k] = obs[k]; oc[k] = fminf(fmaxf(obs[k], -v.clip_obs), v.clip_obs); }
-    v.rew[en] = rew; v.reset[en] = reset; v.progress[en] = progress;
-    v.timeout[en] = (unsigned char)(((float)progress >= tp.max_episode_length - 1.f) && (reset != 0));   // vec_task.py:394
+    store_step_outputs(v, en, obs, rew, reset, progress, tp.max_episode_length);
 }
-static void cartpole_post_env(const View& v, const CartpoleParams& tp, int en, StatAcc& acc) {
-    const int N = v.N;
-    float q[2] = {v.dof[en], v.dof[N + en]}, qd[2] = {v.dof[2 * N + en], v.dof[3 * N + en]};
-    long long progress = v.progress[en] + 1;                   // cartpole.py:165-174
-    int ep = v.episode[en];
-    if (v.reset[en] != 0) {
-        cartpole_reset(v.seed, (uint32_t)(v.env_offset + en), (uint32_t)ep, q, qd);
-        ep += 1;
-        progress = 0;
-        for (int k = 0; k < 2; ++k) { v.dof[k * N + en] = q[k]; v.dof[(2 + k) * N + en] = qd[k]; v.laml[k * N + en] = 0.f; }
-    }
-    float obs[4] = {q[0], qd[0], q[1], qd[1]};                 // cartpole.py:131-142
-    float rew;
-    long long reset;
-    cartpole_reward(tp, obs[2], obs[3], obs[1], obs[0], 0LL, progress, &rew, &reset);
-    if (v.obs_noise.dist != 0)
-        for (int k = 0; k < 4; ++k) obs[k] = apply_noise(v.obs_noise, v.seed, (uint32_t)(v.env_offset + en), v.step, 0u, (uint32_t)k, obs[k]);
-    episode_stats_env(v, en, rew, reset, progress, acc);
-    v.randomize[en] += 1;
-    v.episode[en] = ep;
-    float* ob = v.obs + (size_t)en * 4;
-    float* oc = v.obs_out + ((size_t)v.ring * N + en) * 4;
-    for (int k = 0; k < 4; ++k) { ob[k] = obs[k]; oc[k] = fminf(fmaxf(obs[k], -v.clip_obs), v.clip_obs); }
-    v.rew[en] = rew; v.reset[en] = reset; v.progress[en] = progress;
-    v.timeout[en] = (unsigned char)(((float)progress >= tp.max_episode_length - 1.f) && (reset != 0));
-}
-
 template <class M>
 static void load_tau(const View& v, int en, float* tau) { for (int k = 0; k < M::ND; ++k) tau[k] = v.tau[k * v.N + en]; }
 
@@ -261,7 +219,7 @@ static void step_loco(MiEngine* e, const float* actions) {
         for (int c = 0; c < e->control_freq_inv; ++c) simulate_env<M>(v, e->P, en, tau);
         loco_post_env<M, HUM>(v, tp, en, accs[omp_get_thread_num()]);
     }
-    for (const StatAcc& a : accs) { v.stats[0] += (float)a.fin_ret; v.stats[1] += (float)a.fin_len; v.stats[2] += (float)a.fin; v.stats[3] += (float)a.r; v.stats[4] += (float)a.cnt; }
+    flush_stats(v, accs);
 }
 static void step_cartpole(MiEngine* e, const float* actions) {
     using M = ModelCartpole;
@@ -279,17 +237,13 @@ static void step_cartpole(MiEngine* e, const float* actions) {
         tau[0] = a * tp.max_push_effort; tau[1] = 0.f;            // cartpole.py:159-163: effort on DoF 0 only
         v.tau[en] = tau[0]; v.tau[N + en] = 0.f;
         for (int c = 0; c < e->control_freq_inv; ++c) simulate_env<M>(v, e->P, en, tau);
-        cartpole_post_env(v, tp, en, accs[omp_get_thread_num()]);
+        cartpole_post_env(v, tp, en, HostEpisodeRed{&accs[omp_get_thread_num()]});
     }
-    for (const StatAcc& a : accs) { v.stats[0] += (float)a.fin_ret; v.stats[1] += (float)a.fin_len; v.stats[2] += (float)a.fin; v.stats[3] += (float)a.r; v.stats[4] += (float)a.cnt; }
+    flush_stats(v, accs);
 }
 
-// ---- the small tasks: the per-env bodies of kernels_quadcopter.hip / kernels_ingenuity.hip / kernels_ball_balance.hip, one env at a time
-static inline void write_obs(const View& v, int en, const float* obs, int nobs) {
-    float* ob = v.obs + (size_t)en * nobs;
-    float* oc = v.obs_out + ((size_t)v.ring * v.N + en) * nobs;
-    for (int k = 0; k < nobs; ++k) { ob[k] = obs[k]; oc[k] = fminf(fmaxf(obs[k], -v.clip_obs), v.clip_obs); }
-}
+// ---- the small tasks: pre_physics_step, post_physics_step and the resets are the bodies of tasks/*_step.hpp that the kernels run; the
+// sub-steps between them are this file's own (a stack row store where the kernels use LDS)
 static inline void clamp_angular_speed(float* root, float lim) {      // asset_options.max_angular_velocity
     const float w2 = root[10] * root[10] + root[11] * root[11] + root[12] * root[12];
     if (w2 > lim * lim) { const float sc = lim / sqrtf(w2); root[10] *= sc; root[11] *= sc; root[12] *= sc; }
@@ -309,16 +263,6 @@ static void drive_substeps(const View& v, const SimParams& P, int en, int n_sub,
     }
     store_env(sim, v, en);
 }
-static void quad_reset_env(MiEngine* e, int en) {
-    const View& v = e->v;
-    const int N = v.N;
-    float root[13], q[kQuadDof], qd[kQuadDof];
-    const int ep = v.episode[en];
-    quadcopter_reset(e->quad, v.seed, (uint32_t)(v.env_offset + en), (uint32_t)ep, root, q, qd);
-    for (int k = 0; k < 13; ++k) v.root[k * N + en] = root[k];
-    for (int d = 0; d < kQuadDof; ++d) { v.dof[d * N + en] = q[d]; v.dof[(kQuadDof + d) * N + en] = 0.f; v.laml[d * N + en] = 0.f; }
-    v.episode[en] = ep + 1; v.reset[en] = 0; v.progress[en] = 0;
-}
 static void step_quadcopter(MiEngine* e, const float* actions, bool simulate_only) {
     using QM = ModelQuadcopter;
     const View& v = e->v;
@@ -328,64 +272,14 @@ static void step_quadcopter(MiEngine* e, const float* actions, bool simulate_onl
     std::vector<StatAcc> accs(e->num_threads);
 #pragma omp parallel for schedule(static) num_threads(e->num_threads)
     for (int en = 0; en < N; ++en) {
-        if (!simulate_only) {          // pre_physics_step (quadcopter.py:276-292)
-            const bool rs = v.reset[en] != 0;
-            if (rs) quad_reset_env(e, en);
-            for (int d = 0; d < kQuadDof; ++d) {
-                const float a = fminf(fmaxf(actions[(size_t)en * kQuadAct + d], -p.clip_actions), p.clip_actions);
-                v.actions[d * N + en] = a;
-                float t = qv.targets[d * N + en] + p.dt * p.dof_action_speed_scale * a;
-                t = fmaxf(fminf(t, p.dof_upper[d]), p.dof_lower[d]);
-                if (rs) t = v.dof[d * N + en];
-                qv.targets[d * N + en] = t;
-            }
-            for (int k = 0; k < kQuadRotors; ++k) {
-                const float a = fminf(fmaxf(actions[(size_t)en * kQuadAct + kQuadDof + k], -p.clip_actions), p.clip_actions);
-                v.actions[(kQuadDof + k) * N + en] = a;
-                float th = qv.thrusts[k * N + en] + p.dt * p.thrust_action_speed_scale * a;
-                th = fmaxf(fminf(th, p.max_thrust), 0.f);
-                qv.thrusts[k * N + en] = rs ? 0.f : th;
-                qv.forces[(3 * QM::sens_body[k] + 2) * N + en] = rs ? 0.f : th;
-            }
-        }
+        if (!simulate_only) quad_pre_env(v, qv, p, actions, en);
         float target[kQuadDof], fs[kQuadRotors][3];
         for (int d = 0; d < kQuadDof; ++d) target[d] = qv.targets[d * N + en];
         for (int k = 0; k < kQuadRotors; ++k) { fs[k][0] = fs[k][1] = 0.f; fs[k][2] = qv.forces[(3 * QM::sens_body[k] + 2) * N + en]; }
         drive_substeps<QM, kQuadRotors>(v, e->P, en, (simulate_only ? 1 : e->control_freq_inv) * e->P.substeps, p.drive_stiffness, p.drive_damping, target, &fs[0][0], p.max_angular_velocity);
-        if (simulate_only) continue;
-        float root[13], q[kQuadDof], obs[kQuadObs], rew;     // post_physics_step (:294-302)
-        for (int k = 0; k < 13; ++k) root[k] = v.root[k * N + en];
-        for (int d = 0; d < kQuadDof; ++d) q[d] = v.dof[d * N + en];
-        const long long progress = v.progress[en] + 1;
-        long long reset;
-        quadcopter_observations(root, q, obs);
-        quadcopter_reward(root, progress, p.max_episode_length, &rew, &reset);
-        episode_stats_env(v, en, rew, reset, progress, accs[omp_get_thread_num()]);
-        v.randomize[en] += 1;
-        write_obs(v, en, obs, kQuadObs);
-        v.rew[en] = rew; v.reset[en] = reset; v.progress[en] = progress;
-        v.timeout[en] = (unsigned char)(((float)progress >= p.max_episode_length - 1.f) && (reset != 0));
+        if (!simulate_only) quad_post_env(v, qv, p, en, HostEpisodeRed{&accs[omp_get_thread_num()]});
     }
-    for (const StatAcc& a : accs) { v.stats[0] += (float)a.fin_ret; v.stats[1] += (float)a.fin_len; v.stats[2] += (float)a.fin; v.stats[3] += (float)a.r; v.stats[4] += (float)a.cnt; }
-}
-static void ing_set_target(MiEngine* e, int en, const float* t) {
-    const int N = e->v.N;
-    for (int k = 0; k < 3; ++k) { e->iv.target[k * N + en] = t[k]; e->iv.marker[k * N + en] = t[k] + (k == 2 ? 0.4f : 0.f); }
-}
-static void ing_reset_env(MiEngine* e, int en) {
-    const View& v = e->v;
-    const int N = v.N;
-    const uint32_t genv = (uint32_t)(v.env_offset + en);
-    const int ep = v.episode[en];
-    float root[13], target[3];
-    ingenuity_target(v.seed, genv, (uint32_t)ep, 3u, target);
-    ing_set_target(e, en, target);
-    ingenuity_reset_root(e->ing, v.seed, genv, (uint32_t)ep, root);
-    for (int k = 0; k < 13; ++k) v.root[k * N + en] = root[k];
-    v.dof[(kIngDof + 1) * N + en] = -e->ing.rotor_speed;
-    v.dof[(kIngDof + 3) * N + en] = e->ing.rotor_speed;
-    for (int d = 0; d < kIngDof; ++d) v.laml[d * N + en] = 0.f;
-    v.episode[en] = ep + 1; v.reset[en] = 0; v.progress[en] = 0;
+    flush_stats(v, accs);
 }
 static void step_ingenuity(MiEngine* e, const float* actions, bool simulate_only) {
     using IM = ModelIngenuity;
@@ -396,59 +290,13 @@ static void step_ingenuity(MiEngine* e, const float* actions, bool simulate_only
     std::vector<StatAcc> accs(e->num_threads);
 #pragma omp parallel for schedule(static) num_threads(e->num_threads)
     for (int en = 0; en < N; ++en) {
-        if (!simulate_only) {          // pre_physics_step (ingenuity.py:321-354)
-            const uint32_t genv = (uint32_t)(v.env_offset + en);
-            const long long progress = v.progress[en];
-            float target[3];
-            if (progress % p.target_period == 0) {
-                ingenuity_target(v.seed, genv, (uint32_t)v.episode[en], 8u + 3u * (uint32_t)(progress / p.target_period), target);
-                ing_set_target(e, en, target);
-            }
-            const bool rs = v.reset[en] != 0;
-            if (rs) ing_reset_env(e, en);
-            float a[kIngAct];
-            for (int k = 0; k < kIngAct; ++k) { a[k] = fminf(fmaxf(actions[(size_t)en * kIngAct + k], -p.clip_actions), p.clip_actions); v.actions[k * N + en] = a[k]; }
-            for (int r = 0; r < kIngRotors; ++r) {
-                const float vertical = fminf(fmaxf(a[3 * r + 2] * p.thrust_action_speed_scale, -p.thrust_upper_limit), p.thrust_upper_limit);
-                float th[3];
-                th[2] = p.dt * vertical;
-                for (int k = 0; k < 2; ++k) th[k] = th[2] * fminf(fmaxf(a[3 * r + k], -p.thrust_lateral_component), p.thrust_lateral_component);
-                for (int k = 0; k < 3; ++k) {
-                    const float x = rs ? 0.f : th[k];
-                    iv.thrusts[(3 * r + k) * N + en] = x;
-                    iv.forces[(3 * IM::sens_body[r] + k) * N + en] = x;
-                }
-            }
-        }
+        if (!simulate_only) ing_pre_env(v, iv, p, actions, en);
         float target[kIngDof] = {0}, fs[kIngRotors][3];
         for (int r = 0; r < kIngRotors; ++r) for (int k = 0; k < 3; ++k) fs[r][k] = iv.forces[(3 * IM::sens_body[r] + k) * N + en];
         drive_substeps<IM, kIngRotors>(v, e->P, en, (simulate_only ? 1 : e->control_freq_inv) * e->P.substeps, 0.f, 0.f, target, &fs[0][0], p.max_angular_velocity);
-        if (simulate_only) continue;
-        float root[13], tg[3], obs[kIngObs], rew;          // post_physics_step (:356-365)
-        for (int k = 0; k < 13; ++k) root[k] = v.root[k * N + en];
-        for (int k = 0; k < 3; ++k) tg[k] = iv.target[k * N + en];
-        const long long progress = v.progress[en] + 1;
-        long long reset;
-        ingenuity_observations(root, tg, obs);
-        ingenuity_reward(root, tg, root + 3, root + 10, progress, p.max_episode_length, &rew, &reset);
-        episode_stats_env(v, en, rew, reset, progress, accs[omp_get_thread_num()]);
-        v.randomize[en] += 1;
-        write_obs(v, en, obs, kIngObs);
-        v.rew[en] = rew; v.reset[en] = reset; v.progress[en] = progress;
-        v.timeout[en] = (unsigned char)(((float)progress >= p.max_episode_length - 1.f) && (reset != 0));
+        if (!simulate_only) ing_post_env(v, iv, p, en, HostEpisodeRed{&accs[omp_get_thread_num()]});
     }
-    for (const StatAcc& a : accs) { v.stats[0] += (float)a.fin_ret; v.stats[1] += (float)a.fin_len; v.stats[2] += (float)a.fin; v.stats[3] += (float)a.r; v.stats[4] += (float)a.cnt; }
-}
-static void bbot_reset_env(MiEngine* e, int en) {
-    const View& v = e->v;
-    const int N = v.N;
-    const int ep = v.episode[en];
-    float ball[13];
-    bbot_reset_ball(e->bbot, v.seed, (uint32_t)(v.env_offset + en), (uint32_t)ep, ball);
-    for (int k = 0; k < 13; ++k) { v.root[k * N + en] = v.init_root[k * N + en]; e->bv.ball[k * N + en] = ball[k]; }
-    for (int d = 0; d < kBbotDof; ++d) { v.dof[d * N + en] = 0.f; v.dof[(kBbotDof + d) * N + en] = 0.f; v.laml[d * N + en] = 0.f; }
-    for (int k = 0; k < 9; ++k) e->bv.lamp[k * N + en] = 0.f;
-    v.episode[en] = ep + 1; v.reset[en] = 0; v.progress[en] = 0;
+    flush_stats(v, accs);
 }
 static void step_ball_balance(MiEngine* e, const float* actions, bool simulate_only) {
     using BM = ModelBalanceBot;
@@ -461,18 +309,7 @@ static void step_ball_balance(MiEngine* e, const float* actions, bool simulate_o
     std::vector<StatAcc> accs(e->num_threads);
 #pragma omp parallel for schedule(static) num_threads(e->num_threads)
     for (int en = 0; en < N; ++en) {
-        if (!simulate_only) {          // pre_physics_step (ball_balance.py:395-413)
-            const bool rs = v.reset[en] != 0;
-            if (rs) bbot_reset_env(e, en);
-            float a[kBbotAct];
-            for (int k = 0; k < kBbotAct; ++k) { a[k] = fminf(fmaxf(actions[(size_t)en * kBbotAct + k], -p.clip_actions), p.clip_actions); v.actions[k * N + en] = a[k]; }
-            for (int d = 0; d < kBbotDof; ++d) {
-                float t = bv.targets[d * N + en];
-                if (d & 1) t += p.dt * p.action_speed_scale * a[d >> 1];
-                t = fmaxf(fminf(t, p.dof_upper[d]), p.dof_lower[d]);
-                bv.targets[d * N + en] = rs ? 0.f : t;
-            }
-        }
+        if (!simulate_only) bbot_pre_env(v, bv, p, actions, en);
         BbotSim<BM> sim;
         load_env(sim, v, en);
         float target[kBbotDof];
@@ -487,22 +324,9 @@ static void step_ball_balance(MiEngine* e, const float* actions, bool simulate_o
         store_env(sim, v, en);
         for (int k = 0; k < 3; ++k) { bv.ball[k * N + en] = sim.ball.pos[k]; bv.ball[(7 + k) * N + en] = sim.ball.vel[k]; bv.ball[(10 + k) * N + en] = sim.ball.angvel[k]; }
         for (int k = 0; k < 4; ++k) bv.ball[(3 + k) * N + en] = sim.ball.quat[k];
-        if (simulate_only) continue;
-        float q[kBbotDof], qd[kBbotDof], ball[13], sens[18], obs[kBbotObs], rew;     // post_physics_step (:415-424)
-        for (int d = 0; d < kBbotDof; ++d) { q[d] = v.dof[d * N + en]; qd[d] = v.dof[(kBbotDof + d) * N + en]; }
-        for (int k = 0; k < 13; ++k) ball[k] = bv.ball[k * N + en];
-        for (int k = 0; k < 18; ++k) sens[k] = v.sensor[k * N + en];
-        const long long progress = v.progress[en] + 1;
-        long long reset;
-        bbot_observations(q, qd, ball, sens, obs);
-        bbot_reward(ball, ball + 7, p.ball_radius, v.reset[en], progress, p.max_episode_length, &rew, &reset);
-        episode_stats_env(v, en, rew, reset, progress, accs[omp_get_thread_num()]);
-        v.randomize[en] += 1;
-        write_obs(v, en, obs, kBbotObs);
-        v.rew[en] = rew; v.reset[en] = reset; v.progress[en] = progress;
-        v.timeout[en] = (unsigned char)(((float)progress >= p.max_episode_length - 1.f) && (reset != 0));
+        if (!simulate_only) bbot_post_env(v, bv, p, en, HostEpisodeRed{&accs[omp_get_thread_num()]});
     }
-    for (const StatAcc& a : accs) { v.stats[0] += (float)a.fin_ret; v.stats[1] += (float)a.fin_len; v.stats[2] += (float)a.fin; v.stats[3] += (float)a.r; v.stats[4] += (float)a.cnt; }
+    flush_stats(v, accs);
 }
 
 extern "C" int mi_engine_step(MiEngine* e, const float* actions, void*) {
@@ -567,8 +391,7 @@ static void body_states_all(MiEngine* e) {
 #pragma omp parallel for schedule(static) num_threads(e->num_threads)
     for (int en = 0; en < N; ++en) {
         Sim<M> sim;
-        for (int k = 0; k < 13; ++k) sim.root[k] = v.root[k * N + en];
-        for (int k = 0; k < M::ND; ++k) { sim.q[k] = v.dof[k * N + en]; sim.qd[k] = v.dof[(M::ND + k) * N + en]; }
+        load_env(sim, v, en);
         sfor<M::NB>([&](auto B_) {
             constexpr int b = decltype(B_)::value;
             float o[13];
@@ -631,55 +454,27 @@ static int kinematics_views(MiEngine* e, float* out_j, float* out_h, const char*
 extern "C" int mi_engine_compute_jacobians(MiEngine* e, float* out, void*) { return kinematics_views(e, out, nullptr, "mi_engine_compute_jacobians"); }
 extern "C" int mi_engine_compute_mass_matrices(MiEngine* e, float* out, void*) { return kinematics_views(e, nullptr, out, "mi_engine_compute_mass_matrices"); }
 
-template <class M, bool HUM>
-static void reset_loco(MiEngine* e, const int64_t* ids, int n) {
-    using T = Loco<M::ND, 6 * M::NSENS, HUM>;
-    const View& v = e->v;
-    const int N = v.N;
-    for (int i = 0; i < n; ++i) {
-        const int en = (int)ids[i];
-        if (en < 0 || en >= N) continue;
-        float init_root[13], root[13], q[M::ND], qd[M::ND], pot, prev;
-        for (int k = 0; k < 13; ++k) init_root[k] = v.init_root[k * N + en];
-        const int ep = v.episode[en];
-        T::reset(e->loco, v.seed, (uint32_t)(v.env_offset + en), (uint32_t)ep, init_root, root, q, qd, &pot, &prev);
-        v.episode[en] = ep + 1;
-        for (int k = 0; k < 13; ++k) v.root[k * N + en] = root[k];
-        for (int k = 0; k < M::ND; ++k) { v.dof[k * N + en] = q[k]; v.dof[(M::ND + k) * N + en] = qd[k]; v.laml[k * N + en] = 0.f; }
-        for (int k = 0; k < 3 * M::NSPH; ++k) v.lamc[k * N + en] = 0.f;
-        if (M::NPG > 0 && v.lamp) for (int k = 0; k < 3 * M::NPG; ++k) v.lamp[k * N + en] = 0.f;
-        v.potentials[en] = pot; v.prev_potentials[en] = prev;
-        v.progress[en] = 0; v.reset[en] = 0;
-    }
+// reset_idx(env_ids): ids outside the batch are skipped, a repeated id resets again (the next episode's draws)
+template <class F>
+static void for_env_ids(const View& v, const int64_t* ids, int n, F reset_env) {
+    for (int i = 0; i < n; ++i) if (ids[i] >= 0 && ids[i] < v.N) reset_env((int)ids[i]);
 }
 extern "C" int mi_engine_reset_idx(MiEngine* e, const int64_t* env_ids, int n, void*) {
     if (!e) return fail("null engine");
     if (n <= 0) return 0;
     if (!env_ids) return fail("mi_engine_reset_idx: null env_ids");
     const View& v = e->v;
-    const int N = v.N;
     switch (e->task) {
-        case T_CARTPOLE:
-            for (int i = 0; i < n; ++i) {
-                const int en = (int)env_ids[i];
-                if (en < 0 || en >= N) continue;
-                float q[2], qd[2];
-                const int ep = v.episode[en];
-                cartpole_reset(v.seed, (uint32_t)(v.env_offset + en), (uint32_t)ep, q, qd);
-                v.episode[en] = ep + 1;
-                for (int k = 0; k < 2; ++k) { v.dof[k * N + en] = q[k]; v.dof[(2 + k) * N + en] = qd[k]; v.laml[k * N + en] = 0.f; }
-                v.progress[en] = 0; v.reset[en] = 0;
-            }
-            break;
-        case T_ANT: reset_loco<ModelAnt, false>(e, env_ids, n); break;
-        case T_HUMANOID: reset_loco<ModelHumanoid, true>(e, env_ids, n); break;
-        case T_QUADCOPTER: for (int i = 0; i < n; ++i) if (env_ids[i] >= 0 && env_ids[i] < N) quad_reset_env(e, (int)env_ids[i]); break;
-        case T_INGENUITY: for (int i = 0; i < n; ++i) if (env_ids[i] >= 0 && env_ids[i] < N) ing_reset_env(e, (int)env_ids[i]); break;
+        case T_CARTPOLE: for_env_ids(v, env_ids, n, [&](int en) { cartpole_reset_env(v, en); }); break;
+        case T_ANT: for_env_ids(v, env_ids, n, [&](int en) { loco_reset_env<ModelAnt, false>(v, e->loco, en); }); break;
+        case T_HUMANOID: for_env_ids(v, env_ids, n, [&](int en) { loco_reset_env<ModelHumanoid, true>(v, e->loco, en); }); break;
+        case T_QUADCOPTER: for_env_ids(v, env_ids, n, [&](int en) { float q[kQuadDof]; quad_reset_env(v, e->qv, e->quad, en, q); }); break;
+        case T_INGENUITY: for_env_ids(v, env_ids, n, [&](int en) { ing_reset_env(v, e->iv, e->ing, en, v.episode[en]); }); break;
         case T_BALLBALANCE:
-            for (int i = 0; i < n; ++i) if (env_ids[i] >= 0 && env_ids[i] < N) {
-                bbot_reset_env(e, (int)env_ids[i]);
-                for (int d = 0; d < kBbotDof; ++d) e->bv.targets[d * N + (int)env_ids[i]] = 0.f;
-            }
+            for_env_ids(v, env_ids, n, [&](int en) {
+                bbot_reset_env(v, e->bv, e->bbot, en);
+                for (int d = 0; d < kBbotDof; ++d) e->bv.targets[d * v.N + en] = 0.f;          // the pre step's `rs ? 0 : t`
+            });
             break;
         case T_ANYMAL: case T_ANYMAL_FLAT: cpu_anymal_reset(e, env_ids, n); break;
         case T_SHADOWHAND: case T_ALLEGROHAND: hand_call(e, 2, nullptr, false, env_ids, n, nullptr, nullptr); break;

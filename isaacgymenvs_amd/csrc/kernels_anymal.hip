@@ -8,8 +8,8 @@ namespace mi {
 static_assert(ModelAnymal::ND == kAnymalDof, "anymal dof count");
 
 // The per-env bodies of the task's passes live in tasks/anymal_step.hpp (shared with the CPU backend, cpu/cpu_anymal.cpp); the kernels here
-// supply the launch shapes and the cross-lane reductions: wave shuffles + one atomic per wave and statistic.
-struct DevRed {
+// supply the launch shapes and the cross-lane reductions: wave shuffles + one atomic per wave and statistic (episode(): DevEpisodeRed).
+struct DevRed : DevEpisodeRed {
     __device__ __forceinline__ void cmdnorm(const View& v, float acc) const {
         acc = wave_sum(acc);
         if ((threadIdx.x & 63) == 0 && acc > 0.f) atomicAdd(v.ep_stats + 15, acc);
@@ -27,9 +27,6 @@ struct DevRed {
             }
             atomicAdd(v.ep_stats + 14, lv);
         }
-    }
-    __device__ __forceinline__ void episode(const View& v, int e, bool valid, float rew, long long reset, long long progress) const {
-        episode_stats(v, e, valid, rew, reset, progress);
     }
 };
 

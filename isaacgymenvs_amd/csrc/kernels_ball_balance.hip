@@ -2,11 +2,11 @@
 // keeps a dropped ball in place.  pre kernel = pre_physics_step (deferred resets, position targets), sub-step kernel =
 // gym.simulate on core/bbot_engine.hpp (attractor-pinned feet, ball <-> tray contact), post kernel = post_physics_step.
 // One env per lane, 64 envs per wave; the sub-step keeps its 18 constraint rows in registers (no LDS).
+// The per-env bodies of the pre, post, init and reset kernels live in tasks/ball_balance_step.hpp, shared with the CPU backend
+// (cpu/mi_engine_cpu.cpp); the kernels here are index arithmetic, a bounds check and one call.
 #include "step_kernels.hpp"
-#include "task_views.hpp"
 #include "core/bbot_engine.hpp"
-#include "gen/model_balance_bot.h"
-#include "tasks/ball_balance.hpp"
+#include "tasks/ball_balance_step.hpp"
 
 namespace mi {
 
@@ -14,44 +14,12 @@ using BM = ModelBalanceBot;
 static_assert(BM::ND == kBbotDof && BM::NSENS == kBbotSensors && BM::NB == 7, "balance bot model");
 static_assert(sizeof(BbotPhys) == sizeof(BallBalanceParams) - offsetof(BallBalanceParams, pin_stiffness), "BbotPhys is the tail of BallBalanceParams");
 
-
 static __device__ __forceinline__ const BbotPhys& phys_of(const BallBalanceParams& p) { return *reinterpret_cast<const BbotPhys*>(&p.pin_stiffness); }
-
-static __device__ __forceinline__ void bbot_reset_env(const View& v, const BbotView& bv, const BallBalanceParams& p, int e) {
-    const int N = v.N;
-    const int ep = v.episode[e];
-    float ball[13];
-    bbot_reset_ball(p, v.seed, (uint32_t)(v.env_offset + e), (uint32_t)ep, ball);
-    for (int k = 0; k < 13; ++k) {
-        v.root[k * N + e] = v.init_root[k * N + e];                              // :353
-        bv.ball[k * N + e] = ball[k];
-    }
-    for (int d = 0; d < kBbotDof; ++d) { v.dof[d * N + e] = 0.f; v.dof[(kBbotDof + d) * N + e] = 0.f; v.laml[d * N + e] = 0.f; }   // initial_dof_states (:387)
-    for (int k = 0; k < 9; ++k) bv.lamp[k * N + e] = 0.f;
-    v.episode[e] = ep + 1;
-    v.reset[e] = 0;
-    v.progress[e] = 0;
-}
 
 // pre_physics_step (:395-413)
 __global__ void bbot_pre_kernel(View v, BbotView bv, BallBalanceParams p, const float* __restrict__ actions_in) {
-    MI_NO_CONTRACT
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = v.N;
-    if (e >= N) return;
-    const bool rs = v.reset[e] != 0;
-    if (rs) bbot_reset_env(v, bv, p, e);
-    float a[kBbotAct];
-    for (int k = 0; k < kBbotAct; ++k) {
-        a[k] = fminf(fmaxf(actions_in[(size_t)e * kBbotAct + k], -p.clip_actions), p.clip_actions);   // vec_task.py:374
-        v.actions[k * N + e] = a[k];
-    }
-    for (int d = 0; d < kBbotDof; ++d) {
-        float t = bv.targets[d * N + e];
-        if (d & 1) t += p.dt * p.action_speed_scale * a[d >> 1];                 // actuated dofs 1, 3, 5 (:405)
-        t = fmaxf(fminf(t, p.dof_upper[d]), p.dof_lower[d]);                     // tensor_clamp (:406)
-        bv.targets[d * N + e] = rs ? 0.f : t;                                    // :409
-    }
+    if (e < v.N) bbot_pre_env(v, bv, p, actions_in, e);
 }
 
 // gym.simulate(): one physics sub-step
@@ -73,46 +41,15 @@ __global__ __launch_bounds__(64) void bbot_substep_kernel(View v, BbotView bv, S
     sfor<4>([&](auto K) MI_LAMBDA { bv.ball[(3 + K) * N + e] = sim.ball.quat[K]; });
 }
 
-// post_physics_step (:415-424): progress++, observations, reward
+// post_physics_step (:415-424)
 __global__ __launch_bounds__(64) void bbot_post_kernel(View v, BbotView bv, BallBalanceParams p) {
-    const int e0 = blockIdx.x * 64 + threadIdx.x;
-    const int N = v.N;
-    const bool valid = e0 < N;
-    const int e = valid ? e0 : N - 1;
-    float q[kBbotDof], qd[kBbotDof], ball[13], sens[18];
-    sfor<kBbotDof>([&](auto K) MI_LAMBDA { q[K] = v.dof[K * N + e]; qd[K] = v.dof[(kBbotDof + K) * N + e]; });
-    sfor<13>([&](auto K) MI_LAMBDA { ball[K] = bv.ball[K * N + e]; });
-    sfor<18>([&](auto K) MI_LAMBDA { sens[K] = v.sensor[K * N + e]; });
-    const long long progress = v.progress[e] + 1;
-    float obs[kBbotObs], rew;
-    long long reset;
-    bbot_observations(q, qd, ball, sens, obs);
-    bbot_reward(ball, ball + 7, p.ball_radius, v.reset[e], progress, p.max_episode_length, &rew, &reset);
-    episode_stats(v, e, valid, rew, reset, progress);
-    if (!valid) return;
-    v.randomize[e] += 1;
-    float* ob = v.obs + (size_t)e * kBbotObs;
-    float* oc = v.obs_out + ((size_t)v.ring * N + e) * kBbotObs;
-    sfor<kBbotObs>([&](auto K) MI_LAMBDA { ob[K] = obs[K]; oc[K] = fminf(fmaxf(obs[K], -v.clip_obs), v.clip_obs); });
-    v.rew[e] = rew;
-    v.reset[e] = reset;
-    v.progress[e] = progress;
-    v.timeout[e] = (unsigned char)(((float)progress >= p.max_episode_length - 1.f) && (reset != 0));   // vec_task.py:394
+    bbot_post_env(v, bv, p, (int)(blockIdx.x * 64 + threadIdx.x), DevEpisodeRed{});
 }
 
-// __init__ state (:88-112): bot at the tray height, ball at its spawn pose, zero targets, reset_buf = 1 (vec_task.py:318)
+// __init__ state (:88-112) after init_state_kernel: ball at its spawn pose, zero targets
 __global__ void bbot_init_kernel(View v, BbotView bv, BallBalanceParams p) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = v.N;
-    if (e >= N) return;
-    for (int k = 0; k < 13; ++k) {
-        const float x = (k == 2) ? p.tray_height : (k == 6 ? 1.f : 0.f);
-        v.root[k * N + e] = x; v.init_root[k * N + e] = x;
-        bv.ball[k * N + e] = (k < 3) ? p.ball_init_pos[k] : (k == 6 ? 1.f : 0.f);
-    }
-    for (int d = 0; d < kBbotDof; ++d) bv.targets[d * N + e] = 0.f;
-    for (int k = 0; k < 9; ++k) bv.lamp[k * N + e] = 0.f;
-    bv.ncontact[e] = 0;
+    if (e < v.N) bbot_init_env(v, bv, p, e);
 }
 __global__ void bbot_reset_ids_kernel(View v, BbotView bv, BallBalanceParams p, const long long* __restrict__ ids, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -120,7 +57,7 @@ __global__ void bbot_reset_ids_kernel(View v, BbotView bv, BallBalanceParams p, 
     const int e = (int)ids[i];
     if (e < 0 || e >= v.N) return;
     bbot_reset_env(v, bv, p, e);
-    for (int d = 0; d < kBbotDof; ++d) bv.targets[d * v.N + e] = 0.f;
+    for (int d = 0; d < kBbotDof; ++d) bv.targets[d * v.N + e] = 0.f;          // the pre step's `rs ? 0 : t`
 }
 
 static hipError_t bbot_substeps(const View& v, const BbotView& bv, const SimParams& P, const BallBalanceParams& p, int n, hipStream_t s) {

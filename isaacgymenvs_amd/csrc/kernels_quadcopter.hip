@@ -2,52 +2,20 @@
 // rotors; position-driven rotor joints (DOF_MODE_POS) and thrust forces on the rotor bodies (apply_rigid_body_force_tensors,
 // LOCAL_SPACE).  pre kernel = pre_physics_step (deferred resets, action integration), sub-step kernel = gym.simulate with the
 // engine's Drive extras, post kernel = post_physics_step.  One env per lane, 64 envs per wave.
+// The per-env bodies of the pre, post, init and reset kernels live in tasks/quadcopter_step.hpp, shared with the CPU backend
+// (cpu/mi_engine_cpu.cpp); the kernels here are index arithmetic, a bounds check and one call.
 #include "step_kernels.hpp"
-#include "task_views.hpp"
-#include "gen/model_quadcopter.h"
-#include "tasks/quadcopter.hpp"
+#include "tasks/quadcopter_step.hpp"
 
 namespace mi {
 
 using QM = ModelQuadcopter;
 static_assert(QM::ND == kQuadDof && QM::NSENS == kQuadRotors && QM::NB == 9, "quadcopter model");
 
-
 // pre_physics_step (quadcopter.py:276-292)
 __global__ void quad_pre_kernel(View v, QuadView qv, QuadcopterParams p, const float* __restrict__ actions_in) {
-    MI_NO_CONTRACT
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = v.N;
-    if (e >= N) return;
-    const bool rs = v.reset[e] != 0;
-    float q[kQuadDof];
-    if (rs) {   // reset_idx(reset_env_ids) (:279-281)
-        float root[13], qd[kQuadDof];
-        const int ep = v.episode[e];
-        quadcopter_reset(p, v.seed, (uint32_t)(v.env_offset + e), (uint32_t)ep, root, q, qd);
-        for (int k = 0; k < 13; ++k) v.root[k * N + e] = root[k];
-        for (int d = 0; d < kQuadDof; ++d) { v.dof[d * N + e] = q[d]; v.dof[(kQuadDof + d) * N + e] = 0.f; v.laml[d * N + e] = 0.f; }
-        v.episode[e] = ep + 1;
-        v.reset[e] = 0;
-        v.progress[e] = 0;
-    }
-    for (int d = 0; d < kQuadDof; ++d) {
-        const float a = fminf(fmaxf(actions_in[(size_t)e * kQuadAct + d], -p.clip_actions), p.clip_actions);   // vec_task.py:374
-        v.actions[d * N + e] = a;
-        float t = qv.targets[d * N + e] + p.dt * p.dof_action_speed_scale * a;                                 // :284
-        t = fmaxf(fminf(t, p.dof_upper[d]), p.dof_lower[d]);                                                   // tensor_clamp (:285)
-        if (rs) t = q[d];                                                                                      // :297
-        qv.targets[d * N + e] = t;
-    }
-    for (int k = 0; k < kQuadRotors; ++k) {
-        const float a = fminf(fmaxf(actions_in[(size_t)e * kQuadAct + kQuadDof + k], -p.clip_actions), p.clip_actions);
-        v.actions[(kQuadDof + k) * N + e] = a;
-        float th = qv.thrusts[k * N + e] + p.dt * p.thrust_action_speed_scale * a;                             // :288
-        th = fmaxf(fminf(th, p.max_thrust), 0.f);                                                              // :289
-        // the reference fills `forces` from the thrusts BEFORE it clears both for the reset envs (:291-296)
-        qv.thrusts[k * N + e] = rs ? 0.f : th;
-        qv.forces[(3 * QM::sens_body[k] + 2) * N + e] = rs ? 0.f : th;
-    }
+    if (e < v.N) quad_pre_env(v, qv, p, actions_in, e);
 }
 
 // gym.simulate(): one physics sub-step with the position drives and the rotor thrusts
@@ -79,55 +47,22 @@ __global__ __launch_bounds__(64) void quad_substep_kernel(View v, QuadView qv, S
     store_sim(sim, v, e);
 }
 
-// post_physics_step (:294-302): progress++, observations, reward
+// post_physics_step (:294-302)
 __global__ __launch_bounds__(64) void quad_post_kernel(View v, QuadView qv, QuadcopterParams p) {
-    const int e0 = blockIdx.x * 64 + threadIdx.x;
-    const int N = v.N;
-    const bool valid = e0 < N;
-    const int e = valid ? e0 : N - 1;
-    float root[13], q[kQuadDof];
-    sfor<13>([&](auto K) MI_LAMBDA { root[K] = v.root[K * N + e]; });
-    sfor<kQuadDof>([&](auto K) MI_LAMBDA { q[K] = v.dof[K * N + e]; });
-    const long long progress = v.progress[e] + 1;
-    float obs[kQuadObs], rew;
-    long long reset;
-    quadcopter_observations(root, q, obs);
-    quadcopter_reward(root, progress, p.max_episode_length, &rew, &reset);
-    episode_stats(v, e, valid, rew, reset, progress);
-    if (!valid) return;
-    v.randomize[e] += 1;
-    float* ob = v.obs + (size_t)e * kQuadObs;
-    float* oc = v.obs_out + ((size_t)v.ring * N + e) * kQuadObs;
-    sfor<kQuadObs>([&](auto K) MI_LAMBDA { ob[K] = obs[K]; oc[K] = fminf(fmaxf(obs[K], -v.clip_obs), v.clip_obs); });
-    v.rew[e] = rew;
-    v.reset[e] = reset;
-    v.progress[e] = progress;
-    v.timeout[e] = (unsigned char)(((float)progress >= p.max_episode_length - 1.f) && (reset != 0));   // vec_task.py:394
+    quad_post_env(v, qv, p, (int)(blockIdx.x * 64 + threadIdx.x), DevEpisodeRed{});
 }
 
-// __init__ state (:62-101): craft at the default pose, zero targets / thrusts, reset_buf = 1 (vec_task.py:318)
+// __init__ state (:62-101) after init_state_kernel: zero targets / thrusts
 __global__ void quad_init_kernel(View v, QuadView qv, QuadcopterParams p) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = v.N;
-    if (e >= N) return;
-    for (int k = 0; k < 13; ++k) { const float x = (k == 2) ? p.init_height : (k == 6 ? 1.f : 0.f); v.root[k * N + e] = x; v.init_root[k * N + e] = x; }
-    for (int d = 0; d < kQuadDof; ++d) qv.targets[d * N + e] = 0.f;
-    for (int k = 0; k < kQuadRotors; ++k) qv.thrusts[k * N + e] = 0.f;
-    for (int k = 0; k < 3 * QM::NB; ++k) qv.forces[k * N + e] = 0.f;
+    if (e < v.N) quad_init_env(v, qv, p, e);
 }
 __global__ void quad_reset_ids_kernel(View v, QuadView qv, QuadcopterParams p, const long long* __restrict__ ids, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int e = (int)ids[i], N = v.N;
-    if (e < 0 || e >= N) return;
-    float root[13], q[kQuadDof], qd[kQuadDof];
-    const int ep = v.episode[e];
-    quadcopter_reset(p, v.seed, (uint32_t)(v.env_offset + e), (uint32_t)ep, root, q, qd);
-    for (int k = 0; k < 13; ++k) v.root[k * N + e] = root[k];
-    for (int d = 0; d < kQuadDof; ++d) { v.dof[d * N + e] = q[d]; v.dof[(kQuadDof + d) * N + e] = 0.f; v.laml[d * N + e] = 0.f; }
-    v.episode[e] = ep + 1;
-    v.reset[e] = 0;       // :273-274
-    v.progress[e] = 0;
+    const int e = (int)ids[i];
+    float q[kQuadDof];
+    if (e >= 0 && e < v.N) quad_reset_env(v, qv, p, e, q);
 }
 
 static hipError_t quad_substeps(const View& v, const QuadView& qv, const SimParams& P, const QuadcopterParams& p, int n, hipStream_t s) {

@@ -16,6 +16,7 @@
 #include "core/engine.hpp"
 #include "arena.hpp"
 #include "tasks/locomotion.hpp"
+#include "tasks/loco_step.hpp"
 
 namespace mi {
 
@@ -99,6 +100,12 @@ template <int ACTIVE = 64, bool LIVE_MASK = false>
 __device__ __forceinline__ void episode_stats(const View& v, int e, bool valid, float rew, long long reset, long long progress) {
     episode_stats<ACTIVE, LIVE_MASK>(v, e, valid, rew, reset, progress, valid ? v.ep_ret[e] : 0.f);
 }
+// the job-statistics reduction policy of the per-env post bodies shared with the CPU backend (tasks/*_step.hpp), on a full 64-lane wave
+struct DevEpisodeRed {
+    __device__ __forceinline__ void episode(const View& v, int e, bool valid, float rew, long long reset, long long progress) const {
+        episode_stats(v, e, valid, rew, reset, progress);
+    }
+};
 
 // ------------------------------------------------------------------------------------------------ physics sub-step
 // How a control step is cut into launches (all on the caller's stream, no host sync):
@@ -469,82 +476,25 @@ __global__ __launch_bounds__(post_lanes<M>()) void loco_post_kernel(View v, Loco
     loco_post_env<M, HUM, PL, false, NOISE>(v, tp, e, valid, root, q, qd);
 }
 
-
 template <class M>
 __global__ __launch_bounds__(64) void cartpole_post_kernel(View v, CartpoleParams tp) {
-    const int e0 = blockIdx.x * 64 + threadIdx.x;
-    const int N = v.N;
-    const bool valid = e0 < N;
-    const int e = valid ? e0 : N - 1;
-    float q[2] = {v.dof[e], v.dof[N + e]}, qd[2] = {v.dof[2 * N + e], v.dof[3 * N + e]};
-    long long progress = v.progress[e] + 1;  // cartpole.py:165-174
-    int ep = v.episode[e];
-    if (v.reset[e] != 0) {
-        cartpole_reset(v.seed, (uint32_t)(v.env_offset + e), (uint32_t)ep, q, qd);
-        ep += 1;
-        progress = 0;
-        if (valid) {
-            sfor<2>([&](auto K) MI_LAMBDA { v.dof[K * N + e] = q[K]; v.dof[(2 + K) * N + e] = qd[K]; v.laml[K * N + e] = 0.f; });
-        }
-    }
-    float obs[4] = {q[0], qd[0], q[1], qd[1]};  // cartpole.py:131-142
-    float rew;
-    long long reset;
-    cartpole_reward(tp, obs[2], obs[3], obs[1], obs[0], 0LL, progress, &rew, &reset);
-    if (v.obs_noise.dist != 0)
-        sfor<4>([&](auto K) MI_LAMBDA { obs[K] = apply_noise(v.obs_noise, v.seed, (uint32_t)(v.env_offset + e), v.step, 0u, (uint32_t)K, obs[K]); });
-    episode_stats(v, e, valid, rew, reset, progress);
-    if (!valid) return;
-    v.randomize[e] += 1;
-    v.episode[e] = ep;
-    float* ob = v.obs + (size_t)e * 4;
-    float* oc = v.obs_out + ((size_t)v.ring * N + e) * 4;
-    sfor<4>([&](auto K) MI_LAMBDA { ob[K] = obs[K]; oc[K] = fminf(fmaxf(obs[K], -v.clip_obs), v.clip_obs); });
-    v.rew[e] = rew;
-    v.reset[e] = reset;
-    v.progress[e] = progress;
-    v.timeout[e] = (unsigned char)(((float)progress >= tp.max_episode_length - 1.f) && (reset != 0));
+    cartpole_post_env(v, tp, (int)(blockIdx.x * 64 + threadIdx.x), DevEpisodeRed{});
 }
 
 // ------------------------------------------------------------------------------------------------ indexed reset
 template <class M, bool HUM>
 __global__ void loco_reset_kernel(View v, LocoParams tp, const long long* __restrict__ ids, int n) {
-    using T = Loco<M::ND, 6 * M::NSENS, HUM>;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int e = (int)ids[i], N = v.N;
-    if (e < 0 || e >= N) return;
-    float init_root[13], root[13], q[M::ND], qd[M::ND], pot, prev;
-    for (int k = 0; k < 13; ++k) init_root[k] = v.init_root[k * N + e];
-    const int ep = v.episode[e];
-    T::reset(tp, v.seed, (uint32_t)(v.env_offset + e), (uint32_t)ep, init_root, root, q, qd, &pot, &prev);
-    v.episode[e] = ep + 1;
-    for (int k = 0; k < 13; ++k) v.root[k * N + e] = root[k];
-    for (int k = 0; k < M::ND; ++k) {
-        v.dof[k * N + e] = q[k];
-        v.dof[(M::ND + k) * N + e] = qd[k];
-        v.laml[k * N + e] = 0.f;
-    }
-    for (int k = 0; k < 3 * M::NSPH; ++k) v.lamc[k * N + e] = 0.f;
-    if (M::NPG > 0 && v.lamp) for (int k = 0; k < 3 * M::NPG; ++k) v.lamp[k * N + e] = 0.f;
-    v.potentials[e] = pot;
-    v.prev_potentials[e] = prev;
-    v.progress[e] = 0;
-    v.reset[e] = 0;
+    const int e = (int)ids[i];
+    if (e >= 0 && e < v.N) loco_reset_env<M, HUM>(v, tp, e);
 }
 template <class M>
 __global__ void cartpole_reset_kernel(View v, const long long* __restrict__ ids, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int e = (int)ids[i], N = v.N;
-    if (e < 0 || e >= N) return;
-    float q[2], qd[2];
-    const int ep = v.episode[e];
-    cartpole_reset(v.seed, (uint32_t)(v.env_offset + e), (uint32_t)ep, q, qd);
-    v.episode[e] = ep + 1;
-    for (int k = 0; k < 2; ++k) { v.dof[k * N + e] = q[k]; v.dof[(2 + k) * N + e] = qd[k]; v.laml[k * N + e] = 0.f; }
-    v.progress[e] = 0;
-    v.reset[e] = 0;
+    const int e = (int)ids[i];
+    if (e >= 0 && e < v.N) cartpole_reset_env(v, e);
 }
 
 // Kernels that need more than 48 KB of dynamic LDS must opt in once per device (hipFuncSetAttribute is a per-device setting; a

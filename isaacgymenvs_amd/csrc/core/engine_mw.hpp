@@ -31,6 +31,15 @@
 
 namespace mi {
 
+// Weight of the shared trunk coordinates in a block sweep and its inverse.  nact, the number of active blocks, is a sum of
+// four flags that are exactly 0.f or 1.f, so om = (nact > 1.5f) ? 0.5f * (nact + 1.f) : 1.f is one of 1, 1.5, 2, 2.5 and
+// 1.f / om is picked from four constants: the bits of the correctly rounded division (tests/test_mw_sweep_weights.py).
+MI_HD void sweep_weights(const float nact, float& om, float& iom) {
+    const bool a2 = nact > 1.5f, a3 = nact > 2.5f, a4 = nact > 3.5f;
+    om = a4 ? 2.5f : (a3 ? 2.f : (a2 ? 1.5f : 1.f));
+    iom = a4 ? 0.4f : (a3 ? 0.5f : (a2 ? (1.f / 1.5f) : 1.f));
+}
+
 template <class M>
 struct SimMW : Sim<M> {
     using B = Sim<M>;
@@ -397,30 +406,74 @@ struct SimMW : Sim<M> {
         });
         sfor<NVT>([&](auto I) MI_LAMBDA { rows(X_DW + R * NVT + I) = dw[I]; });
         rows(X_FLG + R) = act;
+        // ---- units of the sweeps in registers
+        struct UBuf { float g[3][M::MAXCHAIN]; float al[3], at[3], vt, lam[3]; };
+        auto load_unit = [&](auto U_, UBuf& Bf, const RowStore<RS> rit) MI_LAMBDA {
+            constexpr int u = decltype(U_)::value;
+            if constexpr (u < NLIM) {
+                constexpr int d = B::limdof(u), gi = OFF + d, row = u;
+                sfor<M::nanc[gi] + 1>([&](auto K) MI_LAMBDA { Bf.g[0][K] = rit(row * M::MAXCHAIN + K); });
+                Bf.al[0] = rit(NROWG * M::MAXCHAIN + row);
+                Bf.at[0] = rit(X_AT + row);
+                Bf.vt = rit(NROWG * M::MAXCHAIN + NROWG + row);
+                Bf.lam[0] = rit(NROWG * M::MAXCHAIN + 2 * NROWG + row);
+            } else if constexpr (u < NUNIT) {
+                constexpr int s = u - NLIM, b = M::sph_body[s], row0 = NLIM + 3 * s;
+                sfor<3>([&](auto K) MI_LAMBDA {
+                    sfor<M::chain_len[b]>([&](auto C) MI_LAMBDA { Bf.g[K][C] = rit((row0 + K) * M::MAXCHAIN + C); });
+                    Bf.al[K] = rit(NROWG * M::MAXCHAIN + row0 + K);
+                    Bf.at[K] = rit(X_AT + row0 + K);
+                    Bf.lam[K] = rit(NROWG * M::MAXCHAIN + 2 * NROWG + row0 + K);
+                });
+                Bf.vt = rit(NROWG * M::MAXCHAIN + NROWG + row0);
+            }
+        };
+        auto unit_on = [&](auto U_) MI_LAMBDA -> bool {
+            constexpr int u = decltype(U_)::value;
+            if constexpr (u < NLIM) return true;
+            else if constexpr (u < NUNIT) return (sph_active >> (u - NLIM) & 1ull) != 0ull;
+            else return false;
+        };
+        // One LDS round trip behind a sweep barrier: every role's contribution to the trunk part of w (the warm start's, then the
+        // last sweep's), the activity flags of the sweep that begins and the rows of the role's first unit are read back to back
+        // into registers of their own, and only then are the contributions added, per coordinate in role order.
+        auto gather = [&](const RowStore<RS> xin, float (&t)[NR][NVT]) MI_LAMBDA {
+            sfor<NR>([&](auto R_) MI_LAMBDA { sfor<NVT>([&](auto T) MI_LAMBDA { t[R_][T] = xin(R_ * NVT + T); }); });
+        };
+        auto scatter = [&](const float (&t)[NR][NVT]) MI_LAMBDA {
+            sfor<NV>([&](auto I) MI_LAMBDA {
+                constexpr int i = I;
+                if constexpr (trunk_gi(i)) { sfor<NR>([&](auto R_) MI_LAMBDA { w[i] += t[R_][tidx(i)]; }); }
+            });
+        };
         MI_STAMP(3);
         bar();
         MI_STAMP(4);
         // ============================================================ P4 (every role): block sweeps
-        // trunk part of w: every role adds all roles' warm-start contributions, in role order
-        sfor<NV>([&](auto I) MI_LAMBDA {
-            constexpr int i = I;
-            if constexpr (trunk_gi(i)) { sfor<NR>([&](auto R_) MI_LAMBDA { constexpr int o = X_DW + R_ * NVT + tidx(i); w[i] += rows(o); }); }
-        });
         {
-            struct UBuf { float g[3][M::MAXCHAIN]; float al[3], at[3], vt, lam[3]; };
             UBuf ub[2];
             float wtl[NVT];                  // trunk part of w as this block sees it during a sweep
+            constexpr int U0 = next_own<R>(-1);
+            int par = 0;                     // it & 1: which half of the double-buffered exchange area holds what this sweep reads
             for (int it = 0; it < P.iters; ++it) {
                 int zero;
                 MI_OPAQUE_ZERO(zero);
                 const RowStore<RS> rit = rows.shifted(zero);
-                const int par = it & 1;
+                const RowStore<RS> xin = rows.shifted((X_DW + par * NR * NVT) * RowStore<RS>::stride);
                 const RowStore<RS> xout = rows.shifted((X_DW + (par ^ 1) * NR * NVT) * RowStore<RS>::stride);
                 const RowStore<RS> fin = rows.shifted((X_FLG + par * NR) * RowStore<RS>::stride), fout = rows.shifted((X_FLG + (par ^ 1) * NR) * RowStore<RS>::stride);
+                // trunk part of w: every role adds all roles' contributions (sweep 0: the warm start's), in role order
+                float t[NR][NVT], f[NR];
+                gather(xin, t);
+                sfor<NR>([&](auto R_) MI_LAMBDA { f[R_] = fin(R_); });
+                if constexpr (U0 < NUNIT) load_unit(std::integral_constant<int, U0>{}, ub[0], rit);
+                MI_PHASE();
+                scatter(t);
                 float nact = 0.f;
-                sfor<NR>([&](auto R_) MI_LAMBDA { nact += fin(R_); });
-                const float om = (nact > 1.5f) ? 0.5f * (nact + 1.f) : 1.f;      // weight of the shared trunk coordinates in this sweep
-                const float iom = 1.f / om;
+                sfor<NR>([&](auto R_) MI_LAMBDA { nact += f[R_]; });
+                float om, iom;                   // weight of the shared trunk coordinates in this sweep, and 1 / om
+                static_assert(NR == 4, "sweep_weights: nact is a sum of four flags");
+                sweep_weights(nact, om, iom);
                 sfor<NV>([&](auto I) MI_LAMBDA { if constexpr (trunk_gi(I)) { constexpr int ti = tidx(I); wtl[ti] = w[I]; } });
                 auto wget = [&](auto GI) MI_LAMBDA -> float {
                     constexpr int gi = decltype(GI)::value;
@@ -431,34 +484,6 @@ struct SimMW : Sim<M> {
                     if constexpr (trunk_gi(gi)) { constexpr int ti = tidx(gi); wtl[ti] += om * val; } else w[gi] += val;
                 };
                 float actn = 0.f;
-                auto load_unit = [&](auto U_, UBuf& Bf) MI_LAMBDA {
-                    constexpr int u = decltype(U_)::value;
-                    if constexpr (u < NLIM) {
-                        constexpr int d = B::limdof(u), gi = OFF + d, row = u;
-                        sfor<M::nanc[gi] + 1>([&](auto K) MI_LAMBDA { Bf.g[0][K] = rit(row * M::MAXCHAIN + K); });
-                        Bf.al[0] = rit(NROWG * M::MAXCHAIN + row);
-                        Bf.at[0] = rit(X_AT + row);
-                        Bf.vt = rit(NROWG * M::MAXCHAIN + NROWG + row);
-                        Bf.lam[0] = rit(NROWG * M::MAXCHAIN + 2 * NROWG + row);
-                    } else if constexpr (u < NUNIT) {
-                        constexpr int s = u - NLIM, b = M::sph_body[s], row0 = NLIM + 3 * s;
-                        sfor<3>([&](auto K) MI_LAMBDA {
-                            sfor<M::chain_len[b]>([&](auto C) MI_LAMBDA { Bf.g[K][C] = rit((row0 + K) * M::MAXCHAIN + C); });
-                            Bf.al[K] = rit(NROWG * M::MAXCHAIN + row0 + K);
-                            Bf.at[K] = rit(X_AT + row0 + K);
-                            Bf.lam[K] = rit(NROWG * M::MAXCHAIN + 2 * NROWG + row0 + K);
-                        });
-                        Bf.vt = rit(NROWG * M::MAXCHAIN + NROWG + row0);
-                    }
-                };
-                auto unit_on = [&](auto U_) MI_LAMBDA -> bool {
-                    constexpr int u = decltype(U_)::value;
-                    if constexpr (u < NLIM) return true;
-                    else if constexpr (u < NUNIT) return (sph_active >> (u - NLIM) & 1ull) != 0ull;
-                    else return false;
-                };
-                constexpr int U0 = next_own<R>(-1);
-                if constexpr (U0 < NUNIT) load_unit(std::integral_constant<int, U0>{}, ub[0]);
                 sfor<NUNIT>([&](auto U_) MI_LAMBDA {
                     constexpr int u = U_;
                     if constexpr (own_unit<R>(u)) {
@@ -466,7 +491,7 @@ struct SimMW : Sim<M> {
                         constexpr int pos = own_pos<R>(u), un = next_own<R>(u);
                         UBuf& Bf = ub[pos & 1];
                         if (unit_on(std::integral_constant<int, un>{}))
-                            load_unit(std::integral_constant<int, un>{}, ub[(pos + 1) & 1]);  // prefetch (no-op past the end)
+                            load_unit(std::integral_constant<int, un>{}, ub[(pos + 1) & 1], rit);  // prefetch (no-op past the end)
                         MI_PHASE();
                         if (!unit_on(std::integral_constant<int, u>{})) return;
                         if constexpr (u < NLIM) {
@@ -518,11 +543,13 @@ struct SimMW : Sim<M> {
                 sfor<NV>([&](auto I) MI_LAMBDA { if constexpr (trunk_gi(I)) { constexpr int ti = tidx(I); xout(R * NVT + ti) = (wtl[ti] - w[I]) * iom; } });
                 fout(R) = actn;
                 bar();
-                sfor<NV>([&](auto I) MI_LAMBDA {
-                    constexpr int i = I;
-                    if constexpr (trunk_gi(i)) { sfor<NR>([&](auto R_) MI_LAMBDA { constexpr int o = R_ * NVT + tidx(i); w[i] += xout(o); }); }
-                });
+                par ^= 1;
             }
+            // the last sweep's contributions (no sweep at all: the warm start's)
+            float t[NR][NVT];
+            gather(rows.shifted((X_DW + par * NR * NVT) * RowStore<RS>::stride), t);
+            MI_PHASE();
+            scatter(t);
         }
         MI_STAMP(5);
         // ============================================================ P5: back to generalised velocity, outputs, integration
